@@ -27,7 +27,17 @@ curve25519-dalek u64 backend) on a bounded sample of the same workload,
 rank 0 at N=1 only -- a reported baseline, also used as an in-bench parity
 check of the sample.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  One process per GPU;
+A plain run (no --full) does the headline's work only: it builds the config-2
+inputs, runs W warm-up (at least 2, one per stream) and K timed steps of the
+pipelined headline, checks the verdicts and prints the line (`value`,
+`ms_per_step`, `parity`).  --full adds everything else described above and
+below (the one-stream figure and roofline, the host entry points, latency,
+configs 3 and 4, ingestion, the CPU baselines) to the same line.
+--dump-outputs DIR writes the verdicts of the last timed headline step to
+DIR/verdicts.npy (float32 0/1 per signature; the inputs are seeded, so two
+builds can be compared file for file).
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full].  One process per GPU;
 gloo only for the barrier and the max-over-ranks timing (the data path has no
 collective).  Under torch.distributed.run (WORLD_SIZE set) each process is one
 rank; a plain `python bench.py --gpus N` with N > 1 starts the N ranks itself
@@ -83,7 +93,15 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-seconds of baseline work")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0 = every CPU this process may use, see host_cpu)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the one-stream figure and roofline, the host entry "
+                         "points, latency, configs 3 and 4, wire ingestion, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the verdicts of the last timed headline step to DIR/verdicts.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def host_cpu():
@@ -358,6 +376,16 @@ def main():
     sig.copy_(torch.from_numpy(sig_h))
     msgs.copy_(torch.from_numpy(msg_h))
     words = (n + 63) // 64
+    if not args.full:
+        # a plain run: the headline's own steps and nothing else
+        line = plain_run(torch, be, dev, stream, ntcrypto, pk, sig, msgs, off, ln, n, L, n_edge, words, expect, args,
+                         barrier, max_over_ranks, world, rank, gen_s)
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        be.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # The headline: launches strictly back to back on one stream.
     # NT_BENCH_STREAMS=2 (A/B only): consecutive steps alternate between two
     # streams (nt_dev_ed25519_verify alternates its two workspaces, so the
@@ -487,25 +515,16 @@ def main():
     # the other two halves of the metric, filled in when their configs have run, so
     # that they sit near the front of the line (a reader of its first few hundred
     # bytes sees all of it): config 4's SHA-512 GB/s and config 3's certificates/s
-    line = {"metric": METRIC, "value": round(value, 1), "unit": "verifies/s", "sha512_gbs": None,
-            "certs_per_s": None, "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs / u64 acc",
-            "data": "synthetic (seeded random keys and 512-B messages, GPU-signed; 1% Appendix-B edge cases "
-                    "from tests/golden/ed25519_corpus.npz)",
-            "config": {"workload": "cfg2: %s verify_strict per GPU, %d-B messages, 1%% edge mix"
-                                   % ("1M" if n == 1_000_000 else str(n), L),
-                       "n_per_gpu": n, "msg_len": L, "edge_cases": n_edge,
-                       "parallelism": "shard-by-index, one process per GPU, no collective"},
-            "roofline": roofline,
-            "parity": {"mismatches_vs_expected": mism, "checked": n * world},
-            "input_gen_s": round(gen_s, 3)}
+    line = result_line(value, ms_per_step, world, args, n, L, n_edge, roofline, mism, n * world, gen_s)
     line["streams"] = nstreams
+    last = outs[(args.steps - 1) % nstreams]  # the headline's last timed step wrote its verdicts here
     if nstreams == 1 and os.environ.get("NT_BENCH_CFG2_PIPE", "1") != "0":
         ts = cfg2_two_streams(torch, be, dev, stream, ntcrypto, pk, sig, msgs, off, ln, n, words,
                               expect, args, barrier, max_over_ranks, world)
+        last_ts = ts.pop("_last")
         progress("cfg2 two streams")
         if os.environ.get("NT_BENCH_HEADLINE", "pipelined") == "pipelined":
+            last = last_ts
             # the headline: the same K batches of 1M, consecutive batches on two
             # streams (each batch's verdicts in its own buffer, both checked); the
             # strictly back-to-back figure stays beside it, and the roofline is
@@ -611,11 +630,105 @@ def main():
         for sub in (line.get("sha512"), line.get("certificates")):
             if sub:
                 sub.pop("_ranks", None)
+    if args.dump_outputs:
+        line["outputs"] = dump_outputs(args.dump_outputs, last, n, world, rank)
     if rank == 0:
         print(json.dumps(line), flush=True)
     be.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def result_line(value, ms_per_step, world, args, n, L, n_edge, roofline, mism, checked, gen_s):
+    """The front of the result line, shared by a plain run and a --full run"""
+    return {"metric": METRIC, "value": round(value, 1), "unit": "verifies/s", "sha512_gbs": None,
+            "certs_per_s": None, "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs / u64 acc",
+            "data": "synthetic (seeded random keys and 512-B messages, GPU-signed; 1% Appendix-B edge cases "
+                    "from tests/golden/ed25519_corpus.npz)",
+            "config": {"workload": "cfg2: %s verify_strict per GPU, %d-B messages, 1%% edge mix"
+                                   % ("1M" if n == 1_000_000 else str(n), L),
+                       "n_per_gpu": n, "msg_len": L, "edge_cases": n_edge,
+                       "parallelism": "shard-by-index, one process per GPU, no collective"},
+            "roofline": roofline,
+            "parity": {"mismatches_vs_expected": mism, "checked": checked},
+            "input_gen_s": round(gen_s, 3)}
+
+
+def plain_run(torch, be, dev, stream, ntcrypto, pk, sig, msgs, off, ln, n, L, n_edge, words, expect, args, barrier,
+              max_over_ranks, world, rank, gen_s):
+    """A run without --full: the headline and nothing beside it.  The same
+    warm-up and timed steps that give `value` in a --full run (config 2,
+    consecutive batches alternating between two streams; with
+    NT_BENCH_HEADLINE=one, NT_BENCH_CFG2_PIPE=0 or NT_BENCH_STREAMS=2 the
+    steps of the one-stream figure instead), the last step's verdicts compared
+    with the expected ones and, with --dump-outputs, written out."""
+    one = (os.environ.get("NT_BENCH_STREAMS", "1") == "2" or os.environ.get("NT_BENCH_CFG2_PIPE", "1") == "0"
+           or os.environ.get("NT_BENCH_HEADLINE", "pipelined") != "pipelined")
+    if not one:
+        ts = cfg2_two_streams(torch, be, dev, stream, ntcrypto, pk, sig, msgs, off, ln, n, words, expect, args,
+                              barrier, max_over_ranks, world)
+        last, nstreams = ts.pop("_last"), 2
+        value, ms_per_step, mism = ts["verifies_per_s"], ts["ms_per_step"], ts["mismatches_vs_expected"]
+    else:
+        nstreams = 2 if os.environ.get("NT_BENCH_STREAMS", "1") == "2" else 1
+        streams = pipeline_streams(torch, be, dev, stream, nstreams)
+        reg = Region(torch, streams, stream)
+        outs = [torch.zeros(words, dtype=torch.int64, device=dev) for _ in range(nstreams)]
+
+        def step(i):
+            be.dev_verify(0, streams[i % nstreams].cuda_stream, ntcrypto.NT_MODE_STRICT, pk.data_ptr(), sig.data_ptr(),
+                          msgs.data_ptr(), nbytes(msgs), off.data_ptr(), ln.data_ptr(), n, outs[i % nstreams].data_ptr())
+
+        barrier()  # inputs and outs were written on `stream`
+        for i in range(args.warmup):
+            step(i)
+        barrier()
+        t0 = time.perf_counter()
+        reg.start()
+        for i in range(args.steps):
+            step(i)
+        reg.end()
+        barrier()
+        wall = max_over_ranks(time.perf_counter() - t0)
+        mism = 0
+        for o in outs[:min(nstreams, args.steps)]:
+            got = np.unpackbits(o.cpu().numpy().view(np.uint8), bitorder="little")[:n].astype(bool)
+            mism += int((got != expect).sum())
+        mism = int(max_over_ranks(mism))
+        last = outs[(args.steps - 1) % nstreams]
+        value, ms_per_step = n * world * args.steps / wall, wall * 1e3 / args.steps
+    progress("cfg2 timed: %.1f M verifies/s" % (value / 1e6))
+    line = result_line(value, ms_per_step, world, args, n, L, n_edge, None, mism,
+                       n * world * min(nstreams, args.steps), gen_s)
+    line["streams"] = nstreams
+    line["mode"] = ("plain: the headline's steps only; --full adds the one-stream figure and roofline, the host "
+                    "entry points, latency, configs 3 and 4 (sha512_gbs, certs_per_s), ingestion and the CPU baselines")
+    if args.dump_outputs:
+        line["outputs"] = dump_outputs(args.dump_outputs, last, n, world, rank)
+    return line
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much, over all ranks
+
+
+def dump_outputs(path, bits, n, world, rank):
+    """--dump-outputs: the verdicts of the last timed headline step (what a caller
+    of nt_dev_ed25519_verify receives, one bit per signature) as 0.0 / 1.0 in
+    float32: DIR/verdicts.npy, or DIR/verdicts_rank<r>.npy per rank of a
+    multi-GPU run.  Beyond DUMP_MAX_BYTES in all, a fixed seeded sample of the
+    positions (ascending), the same from run to run."""
+    v = np.unpackbits(bits.cpu().numpy().view(np.uint8), bitorder="little")[:n].astype(np.float32)
+    cap = DUMP_MAX_BYTES // 2 // 4 // world
+    sampled = n > cap
+    if sampled:
+        v = v[np.sort(np.random.default_rng(64).choice(n, size=cap, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    name = "verdicts.npy" if world == 1 else "verdicts_rank%d.npy" % rank
+    np.save(os.path.join(path, name), v)
+    return {"file": name, "dtype": "float32", "count": int(v.size), "of": n, "sampled": sampled,
+            "accepted": int(v.sum())}
 
 
 def cfg2_two_streams(torch, be, dev, stream, ntcrypto, pk, sig, msgs, off, ln, n, words, expect, args, barrier,
@@ -651,6 +764,7 @@ def cfg2_two_streams(torch, be, dev, stream, ntcrypto, pk, sig, msgs, off, ln, n
     return {"verifies_per_s": round(n * world * args.steps / wall, 1), "ms_per_step": round(wall * 1e3 / args.steps, 3),
             "gpu_ms_per_step": round(reg.ms() / args.steps, 3),
             "mismatches_vs_expected": int(max_over_ranks(mism)),
+            "_last": outs[(args.steps - 1) % 2],  # the last timed step's verdict words (popped by the caller)
             "note": "consecutive 1M batches alternating between two streams on different hardware queues: the "
                     "headline `value` (NT_BENCH_HEADLINE=one makes it the one-stream rate, launches strictly back "
                     "to back, which `one_stream` reports beside it)"}

@@ -51,7 +51,7 @@ def test_two_rank_bench_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--sigs", "8192", "--certs", "2000", "--committee", "10", "--sha-msgs", "256",
-                        "--sha-len", "20000", "--no-cpu", "--no-latency", "--no-ingest"],
+                        "--sha-len", "20000", "--no-cpu", "--no-latency", "--no-ingest", "--full"],
                        env=env, capture_output=True, text=True, timeout=300)
     # every rank's own error lines first (the launcher's tail shows only the first rank to fail)
     errs = [x for x in r.stderr.splitlines() if "Error" in x or "error" in x][:40]
@@ -79,3 +79,32 @@ def test_two_rank_bench_on_one_gpu():
     assert sum(r["certificates"] for r in pr["cfg3"]["per_rank"]) == 2000
     assert sum(r["messages"] for r in pr["cfg4"]["per_rank"]) == 256
     assert all(r["signatures"] == 8192 for r in pr["cfg2"]["per_rank"])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only_and_dumps_its_verdicts(tmp_path):
+    """A run without --full: the result line carries the headline fields and
+    none of the --full legs, and --dump-outputs writes the last timed step's
+    verdicts (float32 0/1, one per signature; 1 % edge cases, so most accept)."""
+    import numpy as np
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--sigs", "8192", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(x) for x in re.findall(r"^\{.*\}$", r.stdout, re.M)]
+    assert len(lines) == 1
+    d = lines[0]
+    assert d["metric"] == bench.METRIC and d["unit"] == "verifies/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    # value and ms_per_step describe the same timed steps
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / 8192 - 1) < 0.01
+    assert d["parity"]["mismatches_vs_expected"] == 0 and d["parity"]["checked"] == 2 * 8192
+    for leg in ("one_stream", "host_api", "latency", "sha512", "certificates", "ingest", "cpu_baseline"):
+        assert leg not in d, leg
+    v = np.load(out / "verdicts.npy")
+    assert v.dtype == np.float32 and v.shape == (8192,)
+    assert set(np.unique(v).tolist()) <= {0.0, 1.0}
+    assert d["outputs"]["accepted"] == int(v.sum()) >= 8192 - 8192 // 100

@@ -16,9 +16,9 @@ for s in $STEPS; do
     tests) timeout -k 10 600 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread \
              --durations 10 > "$OUT/gpu_tests.log" 2>&1 || exit 1 ;;
     smoke) timeout -k 10 240 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || exit 1 ;;
-    bench) timeout -k 10 300 python -u bench.py > "$OUT/bench.log" 2>&1 || exit 1 ;;
-    bench2) timeout -k 10 300 python -u bench.py > "$OUT/bench2.log" 2>&1 || exit 1 ;;
-    trace) timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 -u bench.py \
+    bench) timeout -k 10 300 python -u bench.py --full > "$OUT/bench.log" 2>&1 || exit 1 ;;
+    bench2) timeout -k 10 300 python -u bench.py --full > "$OUT/bench2.log" 2>&1 || exit 1 ;;
+    trace) timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 -u bench.py --full \
              > "$OUT/bench_under_rocprof.log" 2>&1 || exit 1 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
