@@ -355,6 +355,10 @@ NT_HD NT_INLINE void lat_lehmer_batch(LatState& S) {
     // v_rcp_f64 (~1 ulp) instead of the IEEE division sequence: an estimate off
     // by more than the one correction below fails the acceptance test
     double q = floor(a * __builtin_amdgcn_rcp(b));
+#elif defined(NT_LAT_RCP_MODEL)
+    // host test builds only (tests/cpp): the device form with a reciprocal the
+    // harness supplies, so the two corrections below run on the CPU as well
+    double q = floor(a * NT_LAT_RCP_MODEL(b));
 #else
     double q = floor(a / b);
 #endif

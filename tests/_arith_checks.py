@@ -1,0 +1,580 @@
+"""Edge-case checks of the Ed25519 arithmetic in narwhal-tusk_amd/csrc/*.hpp, each
+written once as a function of a *runner* and run twice: on the host build of the
+headers (tests/test_host_arith.py, every CPU run) and on the gfx950 build behind
+the device probe (tests/test_gpu_device_arith.py).  A runner is a `Runner` over a
+library whose bulk entry points share one argument list: `nthb_*` of
+tests/cpp/nt_host_harness.cpp or `ntp_*` of tests/cpp/nt_device_probe.hip.
+
+Every comparison is exact: Python integers, hashlib, or the textbook curve model
+in tests/golden/make_golden.py.  Item i of a device call runs in wave i // 64,
+lane i % 64, which is how the checks below choose what shares a wave.
+"""
+import ctypes
+import functools
+import hashlib
+import importlib.util
+import os
+import random
+
+import numpy as np
+
+P = 2 ** 255 - 19
+L = 2 ** 252 + 27742317777372353535851937790883648493
+SH = [26, 25] * 5
+WEIGHT = [sum(SH[:i]) for i in range(10)]
+M26, M25 = (1 << 26) - 1, (1 << 25) - 1
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+# largest limbs the formulas in ge25519.hpp can feed into mul/sq (see fe25519.hpp header)
+F_MAX = [0xFFFFFB4 + 0x8000000 if i == 0 else (0xFFFFFFC + 0x8000000 if i % 2 == 0 else 0x7FFFFFC + 0x4000000)
+         for i in range(10)]                                   # fe_sub4 of (2x reduced) -> f side only
+G_MAX = [0x7FFFFDA + 0x4000000 if i == 0 else (0x7FFFFFE + 0x4000000 if i % 2 == 0 else 0x3FFFFFE + 0x2000000 + (1 << 18))
+         for i in range(10)]                                   # fe_sub of reduced -> either side
+S_MAX = [2 * M26 if i % 2 == 0 else 2 * M25 + (1 << 18) for i in range(10)]  # sum of two reduced -> sq_wide input
+# fe_sq contract: even limbs < 2^26.1, odd < 2^25.1 (reduced outputs, d y^2 + 1)
+R_MAX = [int(2 ** 26.1) - 1 if i % 2 == 0 else int(2 ** 25.1) - 1 for i in range(10)]
+
+
+def is_reduced(limbs):
+    return all(int(l) <= (M26 if i % 2 == 0 else M25 + (1 << 19)) for i, l in enumerate(limbs))
+
+
+def rand_limbs(rng, mx):
+    return [rng.randint(0, m) for m in mx]
+
+
+def value(limbs):
+    return sum(int(l) << w for l, w in zip(limbs, WEIGHT))
+
+
+def to_limbs(x):
+    out = []
+    for s in SH:
+        out.append(x & ((1 << s) - 1))
+        x >>= s
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def model():
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLD, "make_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+# --------------------------------------------------------------------------
+# the runner
+# --------------------------------------------------------------------------
+def _words(ints, nbytes=32):
+    """ints -> (n, nbytes / 4) little-endian uint32"""
+    buf = b"".join(int(x).to_bytes(nbytes, "little") for x in ints)
+    return np.frombuffer(buf, np.uint32).reshape(len(ints), nbytes // 4).copy()
+
+
+def _ints(arr):
+    """(n, w) uint32 -> ints"""
+    raw = np.ascontiguousarray(arr, np.uint32).tobytes()
+    w = 4 * arr.shape[1]
+    return [int.from_bytes(raw[i:i + w], "little") for i in range(0, len(raw), w)]
+
+
+def _limbs(rows):
+    return np.ascontiguousarray(np.array(rows, dtype=np.uint64).astype(np.uint32).reshape(len(rows), 10))
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+ENTRIES = ["fe_mul", "fe_sq", "fe_sq_wide", "fe_carry", "fe_tobytes", "fe_frombytes", "fe_invert", "sc_reduce512",
+           "sc_muladd", "sc_mul", "sc_reduce_half", "sc_recode_w4", "sc_is_canonical", "sc_halfsize", "hram",
+           "point_checks", "ladder_uv"]
+
+
+class Runner:
+    """Bulk calls into a library of `<prefix><entry>(n, ...)` functions; a nonzero
+    return (a hipError_t on the device) raises."""
+
+    def __init__(self, lib, prefix, name):
+        self.lib, self.prefix, self.name = lib, prefix, name
+
+    def _call(self, entry, n, *args):
+        fn = getattr(self.lib, self.prefix + entry)
+        fn.restype = ctypes.c_int
+        rc = fn(ctypes.c_uint64(n), *args)
+        if rc != 0:
+            raise RuntimeError("%s%s returned %d on %s" % (self.prefix, entry, rc, self.name))
+
+    def _fe_op(self, entry, *ins):
+        arrs = [_limbs(x) for x in ins]
+        n = len(arrs[0])
+        out = np.zeros((n, 10), np.uint32)
+        self._call(entry, n, *[_p(a) for a in arrs], _p(out))
+        return out
+
+    def fe_mul(self, fs, gs):
+        return self._fe_op("fe_mul", fs, gs)
+
+    def fe_sq(self, fs):
+        return self._fe_op("fe_sq", fs)
+
+    def fe_sq_wide(self, fs):
+        return self._fe_op("fe_sq_wide", fs)
+
+    def fe_carry(self, fs):
+        return self._fe_op("fe_carry", fs)
+
+    def fe_tobytes(self, fs):
+        a = _limbs(fs)
+        out = np.zeros((len(a), 8), np.uint32)
+        self._call("fe_tobytes", len(a), _p(a), _p(out))
+        return _ints(out)
+
+    def fe_frombytes(self, ints):
+        a = _words(ints)
+        out = np.zeros((len(a), 10), np.uint32)
+        self._call("fe_frombytes", len(a), _p(a), _p(out))
+        return out
+
+    def fe_invert(self, fs, vt):
+        a = _limbs(fs)
+        out = np.zeros((len(a), 8), np.uint32)
+        self._call("fe_invert", len(a), _p(a), _p(out), ctypes.c_int(int(vt)))
+        return _ints(out)
+
+    def _sc_op(self, entry, *ins, nbytes=32):
+        arrs = [_words(x, nbytes) for x in ins]
+        n = len(arrs[0])
+        out = np.zeros((n, 8), np.uint32)
+        self._call(entry, n, *[_p(a) for a in arrs], _p(out))
+        return out
+
+    def sc_reduce512(self, xs):
+        return _ints(self._sc_op("sc_reduce512", xs, nbytes=64))
+
+    def sc_muladd(self, a, b, c):
+        return _ints(self._sc_op("sc_muladd", a, b, c))
+
+    def sc_mul(self, a, b):
+        return _ints(self._sc_op("sc_mul", a, b))
+
+    def sc_recode_w4(self, xs):
+        """64 signed digits per scalar"""
+        out = self._sc_op("sc_recode_w4", xs)
+        nib = (out[:, :, None] >> (4 * np.arange(8, dtype=np.uint32))[None, None, :]) & 15
+        return ((nib.reshape(len(out), 64).astype(np.int64) ^ 8) - 8).tolist()
+
+    def sc_reduce_half(self, ks):
+        """(magnitude, negative) per scalar"""
+        a = _words(ks)
+        out = np.zeros((len(a), 8), np.uint32)
+        neg = np.zeros(len(a), np.uint32)
+        self._call("sc_reduce_half", len(a), _p(a), _p(out), _p(neg))
+        return list(zip(_ints(out), [int(x) for x in neg]))
+
+    def sc_is_canonical(self, xs):
+        a = _words(xs)
+        out = np.zeros(len(a), np.uint32)
+        self._call("sc_is_canonical", len(a), _p(a), _p(out))
+        return [int(x) for x in out]
+
+    def sc_halfsize(self, ks, lehmer):
+        """(u signed, v, bits, sign word of u) per scalar from sc_halfsize_t<lehmer>"""
+        a = _words(ks)
+        n = len(a)
+        u, v = np.zeros((n, 8), np.uint32), np.zeros((n, 8), np.uint32)
+        neg, bits = np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        self._call("sc_halfsize", n, _p(a), _p(u), _p(neg), _p(v), _p(bits), ctypes.c_int(int(lehmer)))
+        return [(-uu if ng else uu, vv, int(b), int(ng)) for uu, ng, vv, b in zip(_ints(u), neg, _ints(v), bits)]
+
+    def hram(self, Rs, As, buf, offs, lens, fast):
+        """k = H(R || A || buf[off : off + len]) mod L per item"""
+        r = np.frombuffer(b"".join(Rs), np.uint32).copy()
+        a = np.frombuffer(b"".join(As), np.uint32).copy()
+        m = np.frombuffer(bytes(buf) + b"\0", np.uint8).copy()
+        off, ln = np.array(offs, np.uint64), np.array(lens, np.uint64)
+        out = np.zeros((len(offs), 8), np.uint32)
+        self._call("hram", len(offs), _p(r), _p(a), _p(m), ctypes.c_uint64(len(buf)), _p(off), _p(ln), _p(out),
+                   ctypes.c_int(int(fast)))
+        return _ints(out)
+
+    def point_checks(self, encs):
+        """(decodes, [8]P == 0 by doublings, torsion-y of the decoded point, torsion_y_words) per encoding"""
+        e = np.frombuffer(b"".join(encs), np.uint32).copy()
+        out = np.zeros((len(encs), 4), np.uint32)
+        self._call("point_checks", len(encs), _p(e), _p(out))
+        return [tuple(bool(x) for x in row) for row in out]
+
+    def ladder_uv(self, As, Rs, uvb):
+        """encoding of -[u]A - [v]R per item; uvb = (u signed, v, bits) per item"""
+        a = np.frombuffer(b"".join(As), np.uint32).copy()
+        r = np.frombuffer(b"".join(Rs), np.uint32).copy()
+        u = _words([abs(x[0]) for x in uvb])
+        neg = np.array([1 if x[0] < 0 else 0 for x in uvb], np.uint32)
+        v = _words([x[1] for x in uvb])
+        bits = np.array([x[2] for x in uvb], np.int32)
+        out = np.zeros((len(uvb), 8), np.uint32)
+        self._call("ladder_uv", len(uvb), _p(a), _p(r), _p(u), _p(neg), _p(v), _p(bits), _p(out))
+        raw = out.tobytes()
+        return [raw[i:i + 32] for i in range(0, len(raw), 32)]
+
+
+# --------------------------------------------------------------------------
+# field multiply / square at the limb bounds, canonical bytes
+# --------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _fe_mul_cases():
+    rng = random.Random(1)
+    cases = [(F_MAX, G_MAX), (F_MAX, F_MAX[:0] + [min(a, b) for a, b in zip(G_MAX, G_MAX)])]
+    for _ in range(3000):
+        cases.append((rand_limbs(rng, F_MAX), rand_limbs(rng, G_MAX)))
+    for k in range(10):  # single-limb maxima
+        f = [0] * 10
+        f[k] = F_MAX[k]
+        cases.append((f, G_MAX))
+    for k in range(10):
+        g = [0] * 10
+        g[k] = G_MAX[k]
+        cases.append((F_MAX, g))
+    want = [value(f) * value(g) % P for f, g in cases]
+    return cases, want
+
+
+def check_fe_mul_bounds(run):
+    """fe_mul at F_MAX x G_MAX, the single-limb maxima of either side and 3,000
+    random limb vectors under the bounds: value mod p and a reduced output"""
+    cases, want = _fe_mul_cases()
+    out = run.fe_mul([c[0] for c in cases], [c[1] for c in cases])
+    for (f, g), o, w in zip(cases, out, want):
+        assert value(o) % P == w, (run.name, f, g)
+        assert is_reduced(o), (run.name, f, g, list(o))
+
+
+@functools.lru_cache(maxsize=None)
+def _fe_sq_cases():
+    rng = random.Random(2)
+    res = {}
+    for name, mx in (("fe_sq", R_MAX), ("fe_sq_wide", S_MAX)):
+        cases = [mx] + [rand_limbs(rng, mx) for _ in range(3000)]
+        for k in range(10):  # single-limb maxima
+            f = [0] * 10
+            f[k] = mx[k]
+            cases.append(f)
+        res[name] = (cases, [value(f) ** 2 % P for f in cases])
+    return res
+
+
+def check_fe_sq_bounds(run):
+    """fe_sq at R_MAX and fe_sq_wide at S_MAX, single-limb maxima, 3,000 random each"""
+    for name, (cases, want) in _fe_sq_cases().items():
+        out = getattr(run, name)(cases)
+        for f, o, w in zip(cases, out, want):
+            assert value(o) % P == w, (run.name, name, f)
+            assert is_reduced(o), (run.name, name, f, list(o))
+
+
+def check_fe_bytes(run):
+    """fe_tobytes is canonical on p, p + 18, 2^255 - 1, ... and on unreduced
+    limbs; fe_carry keeps the value and reduces the limbs; fe_frombytes drops bit
+    255 and keeps the rest"""
+    vals = [0, 1, P - 1, P, P + 1, P + 18, 2 ** 255 - 1, 2 ** 255 - 20, 19, 2 ** 254]
+    rng = random.Random(3)
+    vals += [rng.randrange(0, 2 ** 255) for _ in range(500)]
+    limbs = [to_limbs(v) for v in vals]
+    # unreduced limb patterns (carry input) also canonicalize
+    limbs += [G_MAX] + [rand_limbs(rng, G_MAX) for _ in range(500)]
+    got = run.fe_tobytes(limbs)
+    for f, g in zip(limbs, got):
+        assert g == value(f) % P, (run.name, f)
+    carried = run.fe_carry(limbs)
+    for f, c in zip(limbs, carried):
+        assert value(c) % P == value(f) % P and is_reduced(c), (run.name, f, list(c))
+    enc = vals + [v | (1 << 255) for v in vals[:64]] + [2 ** 256 - 1]
+    for e, f in zip(enc, run.fe_frombytes(enc)):
+        assert value(f) == e & (2 ** 255 - 1) and is_reduced(f), (run.name, hex(e))
+
+
+# --------------------------------------------------------------------------
+# inversion: chosen wave compositions
+# --------------------------------------------------------------------------
+N_INV_RANDOM = 32768
+
+
+@functools.lru_cache(maxsize=None)
+def inversion_inputs():
+    """(values, z^(p-2) mod p).  Waves of 64 (the list is cut at multiples of 64):
+    on the GPU a wave leaves fe_invert_vt's loop only when a = 0 in all of its
+    lanes, so a lane that finished early runs further full iterations with a = 0
+    -- the zeros and ones beside random values below."""
+    rng = random.Random(11)
+    rnd = lambda: rng.randrange(P)
+    waves = [[0] * 64, [1] * 64,
+             [rnd()] + [0] * 63, [0] * 63 + [rnd()],
+             [1 if i % 2 == 0 else rnd() for i in range(64)]]
+    vals = [v for w in waves for v in w]
+    pw = [1 << k for k in range(255)]                      # 2^k in order: 4 waves
+    vals += pw + [0] * (-len(pw) % 64)
+    pm = [P - (1 << k) for k in range(255)]
+    vals += pm + [1] * (-len(pm) % 64)
+    nc = [P + s for s in range(19)]                        # non-canonical p + s (reduced-size limbs)
+    vals += (nc + [2 ** 255 - 1 - s for s in range(19)] + nc + [rnd() for _ in range(7)])[:64]
+    edge = [0, 1, 2, P - 1, (P - 1) // 2, (P + 1) // 2]
+    vals += [edge[i // 2 % 6] if i % 2 == 0 else rnd() for i in range(64)]
+    # the edge list of the host test
+    more = [0, 1, 2, 3, 19, P - 1, P - 2, P + 1, P + 18, 2 ** 254, 2 ** 255 - 20, 2 ** 128, 2 ** 128 - 1,
+            (P - 1) // 2, (P + 1) // 2, 2 ** 62, 2 ** 62 - 1, 2 ** 30, 2 ** 31 + 1]
+    more += [rng.randrange(1 << rng.randrange(1, 255)) for _ in range(1000)]
+    vals += more + [rnd() for _ in range(-len(more) % 64)]
+    assert len(vals) % 64 == 0
+    vals += [rnd() for _ in range(N_INV_RANDOM)]
+    return vals, [pow(v % P, P - 2, P) for v in vals]
+
+
+def check_inversion(run):
+    """fe_invert_vt == z^(p-2) == fe_invert on every input of inversion_inputs()"""
+    vals, want = inversion_inputs()
+    limbs = [to_limbs(v) for v in vals]
+    vt = run.fe_invert(limbs, 1)
+    for i, (g, w) in enumerate(zip(vt, want)):
+        assert g == w, (run.name, "fe_invert_vt", i // 64, i % 64, hex(vals[i]))
+    fermat = run.fe_invert(limbs, 0)
+    for i, (g, w) in enumerate(zip(fermat, want)):
+        assert g == w, (run.name, "fe_invert", i // 64, i % 64, hex(vals[i]))
+
+
+# --------------------------------------------------------------------------
+# scalars
+# --------------------------------------------------------------------------
+def check_sc_reduce512(run):
+    rng = random.Random(4)
+    xs = [rng.randrange(0, 2 ** 512) for _ in range(2000)]
+    xs += [x % 2 ** 512 for x in (0, L - 1, L, L + 1, 2 ** 512 - 1, L * (2 ** 259))]
+    xs += [2 ** 512 - L, L << 250, (L << 259) - 1, 2 ** 256, 2 ** 256 - 1, 2 ** 252]
+    for x, g in zip(xs, run.sc_reduce512(xs)):
+        assert g == x % L, (run.name, hex(x))
+
+
+def check_sc_mul(run):
+    """sc_muladd and sc_mul on every combination of the edge operands and 2,000
+    random triples, and sc_is_canonical around L"""
+    edges = [0, 1, L - 1, L, 2 ** 252, 2 ** 256 - 1]
+    rng = random.Random(41)
+    tri = [(a, b, c) for a in edges for b in edges for c in edges]
+    tri += [tuple(rng.randrange(2 ** 256) for _ in range(3)) for _ in range(1000)]
+    tri += [tuple(rng.randrange(L) for _ in range(3)) for _ in range(1000)]
+    a, b, c = zip(*tri)
+    for (x, y, z), g in zip(tri, run.sc_muladd(a, b, c)):
+        assert g == (x * y + z) % L, (run.name, "sc_muladd", hex(x), hex(y), hex(z))
+    for (x, y, _), g in zip(tri, run.sc_mul(a, b)):
+        assert g == x * y % L, (run.name, "sc_mul", hex(x), hex(y))
+    ss = [0, 1, L - 2, L - 1, L, L + 1, 2 ** 252, 2 ** 252 - 1, 2 ** 255, 2 ** 255 - 1, 2 ** 256 - 1, L + 2 ** 255,
+          L - 2 ** 32, L + 2 ** 32, L - 2 ** 128, L + 2 ** 128] + [rng.randrange(2 ** 253) for _ in range(200)]
+    for s, g in zip(ss, run.sc_is_canonical(ss)):
+        assert g == int(s < L), (run.name, "sc_is_canonical", hex(s))
+
+
+def check_sc_reduce_half(run):
+    """k < L -> (|k'|, sign) with k' = k or k - L, |k'| <= (L - 1) / 2, and the
+    sign and magnitude reconstruct k mod L"""
+    edges = [0, 1, 2, (L - 1) // 2, (L + 1) // 2, (L + 3) // 2, L - 1, L - 2, (1 << 251) - 1, 1 << 251,
+             (1 << 251) + 1, (1 << 252) - 1, (L - 3) // 2, 1 << 252, L - (1 << 32), (L - 1) // 2 - (1 << 32),
+             (L + 1) // 2 + (1 << 32), (L + 1) // 2 + (1 << 224)]
+    rng = random.Random(42)
+    ks = edges + [rng.randrange(L) for _ in range(2000)]
+    for k, (m, neg) in zip(ks, run.sc_reduce_half(ks)):
+        assert neg == int(k > (L - 1) // 2), (run.name, hex(k))
+        assert m <= (L - 1) // 2, (run.name, hex(k))
+        assert (-m if neg else m) % L == k, (run.name, hex(k))
+
+
+def check_sc_recode_w4(run):
+    """signed radix-16 digits of values of 1 .. 253 bits: every digit but the top
+    one in [-8, 8), and the digits sum back to the input"""
+    rng = random.Random(43)
+    xs = [0]
+    for b in range(1, 254):
+        xs += [1 << (b - 1), (1 << b) - 1, rng.randrange(1 << (b - 1), 1 << b)]
+    xs += [int("8" * n, 16) for n in range(1, 64)] + [int("7" * n, 16) for n in range(1, 64)]
+    xs += [L - 1, (L - 1) // 2, 2 ** 253 - 1]
+    for x, d in zip(xs, run.sc_recode_w4(xs)):
+        assert all(-8 <= t < 8 for t in d), (run.name, hex(x))
+        assert sum(t << (4 * i) for i, t in enumerate(d)) == x, (run.name, hex(x), d)
+        top = (x.bit_length() + 5) >> 2  # the ladder's window count for bits = bitlen
+        assert all(t == 0 for t in d[max(top, 1):]), (run.name, hex(x), d)
+
+
+# --------------------------------------------------------------------------
+# half-size scalars
+# --------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def halfsize_scalars(n_random=20000):
+    """every structured scalar of the two host half-size tests plus random ones"""
+    ks = [L - 1 - i for i in range(64)] + [(1 << 252) + i for i in range(64)] + [(1 << 252) - 1 - i for i in range(64)]
+    ks += [0, 1, 2, 3] + [1 << b for b in range(0, 253)] + [(1 << b) - 1 for b in range(1, 253)]
+    # k / 8L close to a ratio of consecutive Fibonacci numbers -> long runs of quotient 1
+    fa, fb = 1, 1
+    while fb < 1 << 126:
+        fa, fb = fb, fa + fb
+    ks += [(8 * L * fa // fb + d) % L for d in range(-32, 33)]
+    # huge first quotients: k tiny relative to 8L, and 8L / k just above an integer
+    ks += [(8 * L) // q + d for q in (3, 1 << 20, 1 << 31, (1 << 32) + 1, 1 << 40, 1 << 60) for d in range(-3, 4)]
+    L8 = 8 * L
+    ks += [0, 1, 2, 7, 8, 9, L - 1, L - 2, L // 2, (L - 1) // 8, 1 << 127, (1 << 127) + 1, 1 << 128,
+           (1 << 200) + 12345, (1 << 252) - 1, L - (1 << 126), L8 // 3, L8 // 5]
+    ks += [(L8 * j) // (1 << 40) for j in range(1, 6)]
+    ks += [(L8 // q) + d for q in (3, 1 << 33, 1 << 70) for d in (-1, 0, 1)]
+    ks = [k % L for k in ks]
+    rng = random.Random(1234)
+    return tuple(ks + [rng.randrange(L) for _ in range(n_random)])
+
+
+def check_halfsize_properties(ks, res, who):
+    """u == v k (mod 8L), v odd, 0 < v < L, bitlen <= bits <= 253"""
+    L8 = 8 * L
+    for k, (u, v, bits, _) in zip(ks, res):
+        assert (u - v * k) % L8 == 0, (who, hex(k))
+        assert v % 2 == 1 and 0 < v < L, (who, hex(k))
+        assert max(abs(u).bit_length(), v.bit_length()) <= bits <= 253, (who, hex(k), bits)
+
+
+def check_halfsize(run, euclid):
+    """The runner's Lehmer-batched reduction (sc_halfsize_t<true>: on the GPU the
+    quotients come from v_rcp_f64 and one correction step) has the lattice
+    properties, equals the runner's own one-step loop, and equals `euclid` -- the
+    HOST one-step loop on the same scalars -- as sc25519.hpp promises ("lands on
+    the same remainder pairs")."""
+    ks = halfsize_scalars()
+    leh = run.sc_halfsize(ks, 1)
+    check_halfsize_properties(ks, leh, run.name + " lehmer")
+    one = run.sc_halfsize(ks, 0)
+    check_halfsize_properties(ks, one, run.name + " one-step")
+    for k, a, b, c in zip(ks, leh, one, euclid):
+        assert a == b, (run.name, "lehmer != one-step", hex(k), a, b)
+        assert a == c, (run.name, "lehmer != host euclid", hex(k), a, c)
+
+
+# --------------------------------------------------------------------------
+# k = H(R || A || M) mod L at every message alignment
+# --------------------------------------------------------------------------
+HRAM_LENS = (0, 1, 31, 32, 33, 47, 48, 63, 64, 111, 112, 127, 128, 175, 176, 239, 240, 1000)
+
+
+def check_hram(run):
+    """each length at each of the byte offsets 0 .. 7 of an aligned buffer, through
+    the one-block fast path (32-byte messages; other lengths fall through) and the
+    general path, against hashlib"""
+    rng = random.Random(96)
+    buf = bytearray()
+    Rs, As, offs, lens, want = [], [], [], [], []
+    for n in HRAM_LENS:
+        for sh in range(8):
+            while len(buf) % 16:
+                buf.append(rng.getrandbits(8))
+            off = len(buf) + sh
+            buf += bytes(rng.getrandbits(8) for _ in range(sh + n))
+            R = bytes(rng.getrandbits(8) for _ in range(32))
+            A = bytes(rng.getrandbits(8) for _ in range(32))
+            Rs.append(R)
+            As.append(A)
+            offs.append(off)
+            lens.append(n)
+            want.append(int.from_bytes(hashlib.sha512(R + A + bytes(buf[off:off + n])).digest(), "little") % L)
+    for fast in (1, 0):
+        got = run.hram(Rs, As, buf, offs, lens, fast)
+        for g, w, off, n in zip(got, want, offs, lens):
+            assert g == w, (run.name, "fast" if fast else "general", "len", n, "offset", off % 16)
+
+
+# --------------------------------------------------------------------------
+# point decoding and the small-order predicates
+# --------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _point_cases():
+    M = model()
+    encs = list(M.small_order_encodings()) + [M.encode(t) for t in M.TORSION]
+    rng = random.Random(5)
+    for t in M.TORSION:
+        for _ in range(3):
+            encs.append(M.encode(M.padd(t, M.pmul(rng.randrange(1, M.L), M.BASE))))
+    encs += [M.encode(M.pmul(rng.randrange(1, M.L), M.BASE)) for _ in range(20)]
+    encs += list(M.noncanonical_encodings())
+    # y values off the curve (decode fails) and their sign-bit twins
+    y, bad = 2, []
+    while len(bad) < 8:
+        e = y.to_bytes(32, "little")
+        if M.decode(e) is None:
+            bad += [e, (y | 1 << 255).to_bytes(32, "little")]
+        y += 1
+    encs += bad
+    want = []
+    for e in encs:
+        pt = M.decode(e)
+        want.append((pt is not None, None if pt is None else M.is_small(pt)))
+    return encs, want
+
+
+def check_point_checks(run):
+    """ge_frombytes_w's verdict and the three small-order predicates against the
+    model, on canonical, y + p and negative-zero encodings of the torsion points,
+    on mixed-order points T + aB, random points and undecodable encodings"""
+    encs, want = _point_cases()
+    n_small = 0
+    for e, (ok, by_dbl, by_y, by_words), (wok, wsmall) in zip(encs, run.point_checks(encs), want):
+        assert ok == wok, (run.name, e.hex())
+        if ok:
+            assert by_dbl == by_y == by_words == wsmall, (run.name, e.hex(), by_dbl, by_y, by_words)
+            n_small += by_y
+    assert n_small >= 8
+
+
+# --------------------------------------------------------------------------
+# the joint ladder with lane-mixed window counts
+# --------------------------------------------------------------------------
+def _bits(u, v):
+    return max(abs(u).bit_length(), v.bit_length())
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_cases(halfsize):
+    """(A encodings, R encodings, (u, v, bits) per lane, expected encodings) of four
+    waves; halfsize(ks) -> (u, v, bits, ...) per scalar (the host reduction)."""
+    M = model()
+    rng = random.Random(77)
+    pt = lambda: M.encode(M.pmul(rng.randrange(1, M.L), M.BASE))
+    ks = [rng.randrange(L) for _ in range(256)]
+    hs = halfsize(tuple(ks))
+    As, Rs, uvb = [], [], []
+    tors = [M.encode(t) for t in M.TORSION]
+    mixed = [M.encode(M.padd(t, M.pmul(rng.randrange(1, M.L), M.BASE))) for t in M.TORSION[1:]]
+    for i in range(256):
+        wave, lane = divmod(i, 64)
+        k = ks[i]
+        A, R, x = pt(), pt(), hs[i][:3]
+        if wave in (1, 3) and lane in (0, 17, 63):
+            x = (k, 1, 253)  # the trivial vector beside half-size ones: the wave runs 64 windows
+        if wave == 2:
+            u, v = [(0, 1), (1, 1), (-1, 1), (2 ** 128 - 1, 2 ** 128 - 1), (-(2 ** 127), 1), (k, 1)][lane % 6]
+            x = (u, v, _bits(u, v))
+        if wave == 3:
+            A = (tors + mixed)[lane % 15]
+            R = (tors + [M.encode(M.IDENT)])[(lane // 3) % 9]
+        As.append(A)
+        Rs.append(R)
+        uvb.append(x)
+    want = []
+    for A, R, (u, v, _) in zip(As, Rs, uvb):
+        a, r = M.decode(A), M.decode(R)
+        ua = M.pmul(abs(u), a if u < 0 else M.pneg(a))
+        want.append(M.encode(M.padd(ua, M.pmul(v, M.pneg(r)))))
+    return tuple(As), tuple(Rs), tuple(uvb), tuple(want)
+
+
+def check_ladder(run, halfsize):
+    """-[u]A - [v]R per lane equals the model's, in waves whose lanes need
+    different window counts (on the GPU every lane runs its wave's maximum: a
+    short (u, v) beside a 253-bit one takes leading zero windows)"""
+    As, Rs, uvb, want = ladder_cases(halfsize)
+    got = run.ladder_uv(As, Rs, uvb)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (run.name, "wave", i // 64, "lane", i % 64, uvb[i])

@@ -13,13 +13,43 @@ P = 2 ** 255 - 19
 L = 2 ** 252 + 27742317777372353535851937790883648493
 
 _lib = None
+_variants = {}
+
+
+def load_variant(variant, build=True):
+    """build/libnthost<variant>.so: "" the default host build, "_fullgcd" every
+    inversion running all 17 outer iterations (-DNT_GCD_EARLY_EXIT=0), "_rcp" the
+    Lehmer quotient from a reciprocal off by up to 2 ulp (NT_LAT_RCP_MODEL).
+    build=False (GPU test runs, which never compile): the library as build() left it."""
+    if variant not in _variants:
+        target = "build/libnthost%s.so" % variant
+        if build:
+            subprocess.run(["make", "-s", "-C", CPP, target], check=True)
+        _variants[variant] = ctypes.CDLL(os.path.join(CPP, target))
+    return _variants[variant]
+
+
+def runner(variant="", build=True):
+    """the bulk entry points (nthb_*) of a harness build as an _arith_checks.Runner"""
+    import _arith_checks
+    return _arith_checks.Runner(load_variant(variant, build), "nthb_", "host" + variant)
+
+
+def host_halfsize(ks):
+    """sc_halfsize (the kernels' Lehmer form) of the default host build: (u, v, bits, sign word) per
+    scalar.  (A GPU run loads the library first, without building: test_gpu_device_arith.py.)"""
+    return runner("").sc_halfsize(ks, 1)
+
+
+def gcd_neg_count(limbs, variant=""):
+    """how often the inversion of this value negates a matrix row (gcd_lincomb_shift's rare branch)"""
+    return int(load_variant(variant).nth_gcd_neg_count(arr(limbs)))
 
 
 def load():
     global _lib
     if _lib is None:
-        subprocess.run(["make", "-s", "-C", CPP], check=True)
-        _lib = ctypes.CDLL(LIB)
+        _lib = load_variant("")
         _lib.nth_verify.restype = ctypes.c_int
         _lib.nth_verify_trivial.restype = ctypes.c_int
         _lib.nth_sc_halfsize.restype = ctypes.c_int

@@ -1,0 +1,294 @@
+// nt_device_probe.hip -- TEST INFRASTRUCTURE: the device functions of
+// narwhal-tusk_amd/csrc/*.hpp behind one kernel each, compiled for gfx950 with
+// the product's flags, so that the arithmetic tests can hand the GPU build the
+// inputs a signature never steers to it (tests/test_gpu_device_arith.py).
+// Every kernel is a thin wrapper around nt_probe_items.hpp (the same item
+// functions the host harness loops over): thread i of the grid runs item i, so
+// with blocks of kBlock = 256 item i sits in wave i / 64, lane i % 64, and a
+// test chooses what shares a wave.  Each ntp_* entry point takes host pointers,
+// works on device 0 and returns the hipError_t (0 = success).
+// Never linked into libntcrypto.so.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../narwhal-tusk_amd/csrc/kernels_common.hpp"
+#include "nt_probe_items.hpp"
+
+using namespace nt;
+
+namespace {
+
+// A device buffer of `bytes` bytes, filled from `host` (when given); the first
+// error of a chain of buffers and copies is kept in *err.
+struct Dev {
+  void* p = nullptr;
+  hipError_t* err;
+  Dev(hipError_t* e, const void* host, size_t bytes) : err(e) {
+    if (*err != hipSuccess) return;
+    *err = hipMalloc(&p, bytes ? bytes : 1);
+    if (*err == hipSuccess && host && bytes) *err = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+  }
+  Dev(const Dev&) = delete;
+  Dev& operator=(const Dev&) = delete;
+  ~Dev() {
+    if (p) (void)hipFree(p);
+  }
+  void back(void* host, size_t bytes) const {
+    if (*err == hipSuccess && bytes) *err = hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost);
+  }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
+
+inline unsigned grid(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+__device__ inline uint64_t item_index() { return (uint64_t)blockIdx.x * kBlock + threadIdx.x; }
+
+// after the launch: launch error, then the kernel's own
+inline void finish(hipError_t* err) {
+  if (*err != hipSuccess) return;
+  *err = hipGetLastError();
+  if (*err == hipSuccess) *err = hipDeviceSynchronize();
+}
+
+__global__ void __launch_bounds__(kBlock) k_fe_mul(uint64_t n, const uint32_t* f, const uint32_t* g, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_fe_mul(i, f, g, o);
+}
+// which: 0 fe_sq, 1 fe_sq_wide, 2 fe_carry
+__global__ void __launch_bounds__(kBlock) k_fe_unary(uint64_t n, const uint32_t* f, uint32_t* o, int which) {
+  const uint64_t i = item_index();
+  if (i >= n) return;
+  if (which == 0) ntp::item_fe_sq(i, f, o);
+  else if (which == 1) ntp::item_fe_sq_wide(i, f, o);
+  else ntp::item_fe_carry(i, f, o);
+}
+__global__ void __launch_bounds__(kBlock) k_fe_tobytes(uint64_t n, const uint32_t* f, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_fe_tobytes(i, f, o);
+}
+__global__ void __launch_bounds__(kBlock) k_fe_frombytes(uint64_t n, const uint32_t* in, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_fe_frombytes(i, in, o);
+}
+// Lanes past n leave at once, so the wave-level exit of fe_invert_vt sees
+// exactly the lanes the caller filled.
+__global__ void __launch_bounds__(kBlock) k_fe_invert_vt(uint64_t n, const uint32_t* f, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_fe_invert(i, f, o, 1);
+}
+__global__ void __launch_bounds__(kBlock) k_fe_invert(uint64_t n, const uint32_t* f, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_fe_invert(i, f, o, 0);
+}
+__global__ void __launch_bounds__(kBlock) k_sc_reduce512(uint64_t n, const uint32_t* in, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_sc_reduce512(i, in, o);
+}
+__global__ void __launch_bounds__(kBlock)
+    k_sc_muladd(uint64_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_sc_muladd(i, a, b, c, o);
+}
+__global__ void __launch_bounds__(kBlock) k_sc_mul(uint64_t n, const uint32_t* a, const uint32_t* b, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_sc_mul(i, a, b, o);
+}
+__global__ void __launch_bounds__(kBlock) k_sc_reduce_half(uint64_t n, const uint32_t* k, uint32_t* o, uint32_t* neg) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_sc_reduce_half(i, k, o, neg);
+}
+__global__ void __launch_bounds__(kBlock) k_sc_recode_w4(uint64_t n, const uint32_t* s, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_sc_recode_w4(i, s, o);
+}
+__global__ void __launch_bounds__(kBlock) k_sc_is_canonical(uint64_t n, const uint32_t* s, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_sc_is_canonical(i, s, o);
+}
+template <bool LEHMER>
+__global__ void __launch_bounds__(kBlock)
+    k_sc_halfsize(uint64_t n, const uint32_t* k, uint32_t* u, uint32_t* uneg, uint32_t* v, int32_t* bits) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_sc_halfsize(i, k, u, uneg, v, bits, LEHMER ? 1 : 0);
+}
+template <bool FAST>
+__global__ void __launch_bounds__(kBlock) k_hram(uint64_t n, const uint32_t* R, const uint32_t* A, const uint8_t* msg,
+                                                 const uint64_t* off, const uint64_t* len, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_hram(i, R, A, msg, off, len, o, FAST ? 1 : 0);
+}
+__global__ void __launch_bounds__(kBlock) k_point_checks(uint64_t n, const uint32_t* enc, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_point_checks(i, enc, o);
+}
+// Lanes past n run the last item again (and write nothing): wave_max shuffles
+// across all 64 lanes of a wave, so every lane of a launched wave stays active.
+__global__ void __launch_bounds__(kBlock)
+    k_ladder_uv(uint64_t n, const uint32_t* A, const uint32_t* R, const uint32_t* u, const uint32_t* uneg,
+                const uint32_t* v, const int32_t* bits, uint4* ws, uint32_t* o) {
+  const uint64_t i = item_index();
+  WsATab at{ws, blockIdx.x};
+  ntp::item_ladder_uv(i < n ? i : n - 1, A, R, u, uneg, v, bits, at, o, i < n);
+}
+
+}  // namespace
+
+#define NTP_BEGIN                      \
+  hipError_t err = hipSetDevice(0);    \
+  if (n == 0) return (int)err;
+#define NTP_LAUNCH(kernel, ...) \
+  if (err == hipSuccess) hipLaunchKernelGGL(kernel, dim3(grid(n)), dim3(kBlock), 0, 0, n, __VA_ARGS__); \
+  finish(&err);
+
+extern "C" {
+
+int ntp_fe_mul(uint64_t n, const uint32_t* f, const uint32_t* g, uint32_t* out) {
+  NTP_BEGIN
+  Dev df(&err, f, 40 * n), dg(&err, g, 40 * n), dout(&err, nullptr, 40 * n);
+  NTP_LAUNCH(k_fe_mul, df.as<uint32_t>(), dg.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out, 40 * n);
+  return (int)err;
+}
+static int fe_unary(uint64_t n, const uint32_t* f, uint32_t* out, int which) {
+  NTP_BEGIN
+  Dev df(&err, f, 40 * n), dout(&err, nullptr, 40 * n);
+  NTP_LAUNCH(k_fe_unary, df.as<uint32_t>(), dout.as<uint32_t>(), which)
+  dout.back(out, 40 * n);
+  return (int)err;
+}
+int ntp_fe_sq(uint64_t n, const uint32_t* f, uint32_t* out) { return fe_unary(n, f, out, 0); }
+int ntp_fe_sq_wide(uint64_t n, const uint32_t* f, uint32_t* out) { return fe_unary(n, f, out, 1); }
+int ntp_fe_carry(uint64_t n, const uint32_t* f, uint32_t* out) { return fe_unary(n, f, out, 2); }
+int ntp_fe_tobytes(uint64_t n, const uint32_t* f, uint32_t* out8) {
+  NTP_BEGIN
+  Dev df(&err, f, 40 * n), dout(&err, nullptr, 32 * n);
+  NTP_LAUNCH(k_fe_tobytes, df.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  return (int)err;
+}
+int ntp_fe_frombytes(uint64_t n, const uint32_t* in8, uint32_t* out) {
+  NTP_BEGIN
+  Dev din(&err, in8, 32 * n), dout(&err, nullptr, 40 * n);
+  NTP_LAUNCH(k_fe_frombytes, din.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out, 40 * n);
+  return (int)err;
+}
+int ntp_fe_invert(uint64_t n, const uint32_t* f, uint32_t* out8, int vt) {
+  NTP_BEGIN
+  Dev df(&err, f, 40 * n), dout(&err, nullptr, 32 * n);
+  if (vt) {
+    NTP_LAUNCH(k_fe_invert_vt, df.as<uint32_t>(), dout.as<uint32_t>())
+  } else {
+    NTP_LAUNCH(k_fe_invert, df.as<uint32_t>(), dout.as<uint32_t>())
+  }
+  dout.back(out8, 32 * n);
+  return (int)err;
+}
+int ntp_sc_reduce512(uint64_t n, const uint32_t* in16, uint32_t* out8) {
+  NTP_BEGIN
+  Dev din(&err, in16, 64 * n), dout(&err, nullptr, 32 * n);
+  NTP_LAUNCH(k_sc_reduce512, din.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  return (int)err;
+}
+int ntp_sc_muladd(uint64_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out8) {
+  NTP_BEGIN
+  Dev da(&err, a, 32 * n), db(&err, b, 32 * n), dc(&err, c, 32 * n), dout(&err, nullptr, 32 * n);
+  NTP_LAUNCH(k_sc_muladd, da.as<uint32_t>(), db.as<uint32_t>(), dc.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  return (int)err;
+}
+int ntp_sc_mul(uint64_t n, const uint32_t* a, const uint32_t* b, uint32_t* out8) {
+  NTP_BEGIN
+  Dev da(&err, a, 32 * n), db(&err, b, 32 * n), dout(&err, nullptr, 32 * n);
+  NTP_LAUNCH(k_sc_mul, da.as<uint32_t>(), db.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  return (int)err;
+}
+int ntp_sc_reduce_half(uint64_t n, const uint32_t* k8, uint32_t* out8, uint32_t* neg) {
+  NTP_BEGIN
+  Dev dk(&err, k8, 32 * n), dout(&err, nullptr, 32 * n), dneg(&err, nullptr, 4 * n);
+  NTP_LAUNCH(k_sc_reduce_half, dk.as<uint32_t>(), dout.as<uint32_t>(), dneg.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  dneg.back(neg, 4 * n);
+  return (int)err;
+}
+int ntp_sc_recode_w4(uint64_t n, const uint32_t* s8, uint32_t* out8) {
+  NTP_BEGIN
+  Dev ds(&err, s8, 32 * n), dout(&err, nullptr, 32 * n);
+  NTP_LAUNCH(k_sc_recode_w4, ds.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  return (int)err;
+}
+int ntp_sc_is_canonical(uint64_t n, const uint32_t* s8, uint32_t* out1) {
+  NTP_BEGIN
+  Dev ds(&err, s8, 32 * n), dout(&err, nullptr, 4 * n);
+  NTP_LAUNCH(k_sc_is_canonical, ds.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out1, 4 * n);
+  return (int)err;
+}
+int ntp_sc_halfsize(uint64_t n, const uint32_t* k8, uint32_t* u8, uint32_t* uneg, uint32_t* v8, int32_t* bits,
+                    int lehmer) {
+  NTP_BEGIN
+  Dev dk(&err, k8, 32 * n), du(&err, nullptr, 32 * n), dn(&err, nullptr, 4 * n), dv(&err, nullptr, 32 * n),
+      db(&err, nullptr, 4 * n);
+  if (lehmer) {
+    NTP_LAUNCH(k_sc_halfsize<true>, dk.as<uint32_t>(), du.as<uint32_t>(), dn.as<uint32_t>(), dv.as<uint32_t>(),
+               db.as<int32_t>())
+  } else {
+    NTP_LAUNCH(k_sc_halfsize<false>, dk.as<uint32_t>(), du.as<uint32_t>(), dn.as<uint32_t>(), dv.as<uint32_t>(),
+               db.as<int32_t>())
+  }
+  du.back(u8, 32 * n);
+  dn.back(uneg, 4 * n);
+  dv.back(v8, 32 * n);
+  db.back(bits, 4 * n);
+  return (int)err;
+}
+// msg: one buffer of msg_bytes bytes (copied to a 256-byte aligned device
+// allocation, so byte offset off[i] fixes message i's alignment); every
+// off[i] + len[i] <= msg_bytes is checked here, before anything is launched
+int ntp_hram(uint64_t n, const uint32_t* R8, const uint32_t* A8, const uint8_t* msg, uint64_t msg_bytes,
+             const uint64_t* off, const uint64_t* len, uint32_t* out8, int fast) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (!msg_slice(off[i], len[i], msg_bytes).ok) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  // load_words reads whole 4-byte granules: keep the allocation a multiple of 16 past the end
+  const size_t padded = (size_t)((msg_bytes + 15) / 16 * 16 + 16);
+  Dev dR(&err, R8, 32 * n), dA(&err, A8, 32 * n), dm(&err, nullptr, padded), doff(&err, off, 8 * n),
+      dlen(&err, len, 8 * n), dout(&err, nullptr, 32 * n);
+  if (err == hipSuccess) err = hipMemset(dm.p, 0, padded);
+  if (err == hipSuccess && msg_bytes) err = hipMemcpy(dm.p, msg, msg_bytes, hipMemcpyHostToDevice);
+  if (fast) {
+    NTP_LAUNCH(k_hram<true>, dR.as<uint32_t>(), dA.as<uint32_t>(), dm.as<uint8_t>(), doff.as<uint64_t>(),
+               dlen.as<uint64_t>(), dout.as<uint32_t>())
+  } else {
+    NTP_LAUNCH(k_hram<false>, dR.as<uint32_t>(), dA.as<uint32_t>(), dm.as<uint8_t>(), doff.as<uint64_t>(),
+               dlen.as<uint64_t>(), dout.as<uint32_t>())
+  }
+  dout.back(out8, 32 * n);
+  return (int)err;
+}
+int ntp_point_checks(uint64_t n, const uint32_t* enc8, uint32_t* out4) {
+  NTP_BEGIN
+  Dev de(&err, enc8, 32 * n), dout(&err, nullptr, 16 * n);
+  NTP_LAUNCH(k_point_checks, de.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out4, 16 * n);
+  return (int)err;
+}
+int ntp_ladder_uv(uint64_t n, const uint32_t* A8, const uint32_t* R8, const uint32_t* u8, const uint32_t* uneg,
+                  const uint32_t* v8, const int32_t* bits, uint32_t* out8) {
+  NTP_BEGIN
+  for (uint64_t i = 0; i < n; ++i)  // 4 W <= 256 digits of the recoded strings
+    if (bits[i] < 0 || bits[i] > 253) return (int)hipErrorInvalidValue;
+  const size_t ws_bytes = (size_t)grid(n) * kBlock * kAEntries * kAQuads * sizeof(uint4);
+  Dev dA(&err, A8, 32 * n), dR(&err, R8, 32 * n), du(&err, u8, 32 * n), dn(&err, uneg, 4 * n), dv(&err, v8, 32 * n),
+      db(&err, bits, 4 * n), dws(&err, nullptr, ws_bytes), dout(&err, nullptr, 32 * n);
+  NTP_LAUNCH(k_ladder_uv, dA.as<uint32_t>(), dR.as<uint32_t>(), du.as<uint32_t>(), dn.as<uint32_t>(),
+             dv.as<uint32_t>(), db.as<int32_t>(), dws.as<uint4>(), dout.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  return (int)err;
+}
+
+}  // extern "C"

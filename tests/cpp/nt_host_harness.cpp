@@ -11,12 +11,30 @@
 #include <cstring>
 #include <unordered_map>
 
+#ifdef NT_LAT_RCP_MODEL
+// build/libnthost_rcp.so: the reciprocal lat_lehmer_batch's device form multiplies by, as a
+// model of v_rcp_f64 -- 1 / b moved by -2 .. +2 ulp, the steps drawn from a fixed-seed
+// generator (xorshift64; one sequence per thread)
+#include <cmath>
+#include <cstdint>
+inline double nth_rcp_model(double b) {
+  static thread_local uint64_t x = 0x9e3779b97f4a7c15ull;
+  x ^= x << 13;
+  x ^= x >> 7;
+  x ^= x << 17;
+  const int step = (int)((x >> 32) % 5u) - 2;
+  double r = 1.0 / b;
+  for (int i = 0; i < (step < 0 ? -step : step); ++i) r = std::nextafter(r, step < 0 ? 0.0 : INFINITY);
+  return r;
+}
+#endif
 #include "../../narwhal-tusk_amd/csrc/ed25519_ops.hpp"
 #include "../../narwhal-tusk_amd/csrc/fe_inv_vt.hpp"
 #include "../../narwhal-tusk_amd/csrc/ks_plan.hpp"
 #include "../../narwhal-tusk_amd/csrc/pipe_plan.hpp"
 #include "../../narwhal-tusk_amd/csrc/key_table.hpp"
 #include "../../narwhal-tusk_amd/csrc/small_model.hpp"
+#include "nt_probe_items.hpp"
 
 namespace nt {
 unsigned long long g_fe_mul = 0, g_fe_sq = 0;
@@ -566,5 +584,152 @@ void nth_key_table_find(const uint8_t* keys, uint32_t nkeys, unsigned long long 
   nt::KeyTable t;
   t.build(keys, nkeys, seed);
   for (unsigned long long i = 0; i < nq; ++i) out[i] = t.find(q + 32 * i);
+}
+}
+
+// ---- host twins of the device probe (nt_device_probe.hip): the same item functions
+// (nt_probe_items.hpp) in a loop over n items, same argument lists as the ntp_* entry points
+extern "C" {
+int nthb_fe_mul(uint64_t n, const uint32_t* f, const uint32_t* g, uint32_t* out) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_mul(i, f, g, out);
+  return 0;
+}
+int nthb_fe_sq(uint64_t n, const uint32_t* f, uint32_t* out) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_sq(i, f, out);
+  return 0;
+}
+int nthb_fe_sq_wide(uint64_t n, const uint32_t* f, uint32_t* out) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_sq_wide(i, f, out);
+  return 0;
+}
+int nthb_fe_carry(uint64_t n, const uint32_t* f, uint32_t* out) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_carry(i, f, out);
+  return 0;
+}
+int nthb_fe_tobytes(uint64_t n, const uint32_t* f, uint32_t* out8) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_tobytes(i, f, out8);
+  return 0;
+}
+int nthb_fe_frombytes(uint64_t n, const uint32_t* in8, uint32_t* out) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_frombytes(i, in8, out);
+  return 0;
+}
+int nthb_fe_invert(uint64_t n, const uint32_t* f, uint32_t* out8, int vt) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_invert(i, f, out8, vt);
+  return 0;
+}
+int nthb_sc_reduce512(uint64_t n, const uint32_t* in16, uint32_t* out8) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_reduce512(i, in16, out8);
+  return 0;
+}
+int nthb_sc_muladd(uint64_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out8) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_muladd(i, a, b, c, out8);
+  return 0;
+}
+int nthb_sc_mul(uint64_t n, const uint32_t* a, const uint32_t* b, uint32_t* out8) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_mul(i, a, b, out8);
+  return 0;
+}
+int nthb_sc_reduce_half(uint64_t n, const uint32_t* k8, uint32_t* out8, uint32_t* neg) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_reduce_half(i, k8, out8, neg);
+  return 0;
+}
+int nthb_sc_recode_w4(uint64_t n, const uint32_t* s8, uint32_t* out8) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_recode_w4(i, s8, out8);
+  return 0;
+}
+int nthb_sc_is_canonical(uint64_t n, const uint32_t* s8, uint32_t* out1) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_is_canonical(i, s8, out1);
+  return 0;
+}
+// lehmer 1: sc_halfsize_t<true> (the kernels'), 0: sc_halfsize_t<false> = sc_halfsize_euclid
+int nthb_sc_halfsize(uint64_t n, const uint32_t* k8, uint32_t* u8, uint32_t* uneg, uint32_t* v8, int32_t* bits,
+                     int lehmer) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_halfsize(i, k8, u8, uneg, v8, bits, lehmer);
+  return 0;
+}
+int nthb_hram(uint64_t n, const uint32_t* R8, const uint32_t* A8, const uint8_t* msg, uint64_t msg_bytes,
+              const uint64_t* off, const uint64_t* len, uint32_t* out8, int fast) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (!msg_slice(off[i], len[i], msg_bytes).ok) return 1;
+  // load_words reads whole 4-byte granules: an aligned copy with room past the end
+  std::vector<uint32_t> buf(msg_bytes / 4 + 8, 0u);
+  if (msg_bytes) std::memcpy(buf.data(), msg, msg_bytes);
+  for (uint64_t i = 0; i < n; ++i) ntp::item_hram(i, R8, A8, (const uint8_t*)buf.data(), off, len, out8, fast);
+  return 0;
+}
+int nthb_point_checks(uint64_t n, const uint32_t* enc8, uint32_t* out4) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_point_checks(i, enc8, out4);
+  return 0;
+}
+// per item with the item's own window count (wave_max is the identity on the host)
+int nthb_ladder_uv(uint64_t n, const uint32_t* A8, const uint32_t* R8, const uint32_t* u8, const uint32_t* uneg,
+                   const uint32_t* v8, const int32_t* bits, uint32_t* out8) {
+  for (uint64_t i = 0; i < n; ++i) {
+    if (bits[i] < 0 || bits[i] > 253) return 1;
+    HostATab at;
+    ntp::item_ladder_uv(i, A8, R8, u8, uneg, v8, bits, at, out8, true);
+  }
+  return 0;
+}
+
+// How often fe_invert_vt's matrix application comes out negative for the value z (10 limbs),
+// i.e. how often gcd_lincomb_shift takes its negation branch (fe_inv_vt.hpp: about once in
+// 3,000 inversions).  The outer loop of fe_invert_vt is restated here around the header's own
+// gcd_len / gcd_bits32 / gcd_lincomb_shift, whose return value is what is counted (u and v do
+// not influence it and are left out); returns -1 if the restated loop does not end in
+// a = 0, b = 1 for z != 0 (it has then drifted from the header).
+int nth_gcd_neg_count(const uint32_t* f) {
+  fe z;
+  std::memcpy(z.v, f, 40);
+  uint32_t w[8];
+  fe_tobytes_w(w, z);
+  uint32_t a[9], b[9], zero = 0;
+  for (int i = 0; i < 9; ++i) {
+    const int bit = 30 * i, q = bit >> 5, r = bit & 31;
+    uint64_t x = (uint64_t)w[q];
+    if (q + 1 < 8) x |= (uint64_t)w[q + 1] << 32;
+    a[i] = (uint32_t)(x >> r) & kM30;
+    b[i] = i == 0 ? kM30 - 18u : (i < 8 ? kM30 : 0x7fffu);
+    zero |= a[i];
+  }
+  zero = zero == 0;
+  int count = 0;
+  for (int it = 0; it < kGcdOuter; ++it) {
+    uint32_t ab[9];
+    for (int i = 0; i < 9; ++i) ab[i] = a[i] | b[i];
+    uint32_t nb = gcd_len(ab);
+    nb = nb > 62u ? nb : 62u;
+    uint64_t A = (uint64_t)a[0] | ((uint64_t)gcd_bits32(a, nb - 32u) << 30);
+    uint64_t B = (uint64_t)b[0] | ((uint64_t)gcd_bits32(b, nb - 32u) << 30);
+    int64_t f0 = 1, g0 = 0, f1 = 0, g1 = 1;
+    for (int j = 0; j < kGcdInner; ++j) {
+      if (A & 1u) {
+        if (A < B) {
+          std::swap(A, B);
+          std::swap(f0, f1);
+          std::swap(g0, g1);
+        }
+        A -= B;
+        f0 -= f1;
+        g0 -= g1;
+      }
+      A >>= 1;
+      f1 *= 2;
+      g1 *= 2;
+    }
+    uint32_t na[9], nbv[9];
+    count += (int)gcd_lincomb_shift(na, a, b, (int32_t)f0, (int32_t)g0);
+    count += (int)gcd_lincomb_shift(nbv, a, b, (int32_t)f1, (int32_t)g1);
+    for (int i = 0; i < 9; ++i) {
+      a[i] = na[i];
+      b[i] = nbv[i];
+    }
+  }
+  uint32_t anz = 0, bone = b[0] ^ 1u;
+  for (int i = 0; i < 9; ++i) anz |= a[i];
+  for (int i = 1; i < 9; ++i) bone |= b[i];
+  if (!zero && (anz != 0 || bone != 0)) return -1;
+  return count;
 }
 }

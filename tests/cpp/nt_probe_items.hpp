@@ -1,0 +1,187 @@
+// nt_probe_items.hpp -- TEST INFRASTRUCTURE: item i of every arithmetic probe,
+// written once and run two ways: by one GPU thread each in nt_device_probe.hip
+// (the gfx950 build of narwhal-tusk_amd/csrc/*.hpp) and in a loop by
+// nt_host_harness.cpp (the same headers compiled by g++).  Each function is a
+// thin wrapper: it moves item i's words in and out of flat arrays and calls the
+// header function under test; no arithmetic lives here.
+// Field elements are 10 limbs, encodings and scalars 8 little-endian words.
+#pragma once
+#include "../../narwhal-tusk_amd/csrc/ed25519_ops.hpp"
+#include "../../narwhal-tusk_amd/csrc/fe_inv_vt.hpp"
+
+namespace ntp {
+using namespace nt;
+
+NT_HD NT_INLINE void ld_fe(fe& a, const uint32_t* p, size_t i) {
+#pragma unroll
+  for (int l = 0; l < 10; ++l) a.v[l] = p[10 * i + l];
+}
+NT_HD NT_INLINE void st_fe(uint32_t* p, size_t i, const fe& a) {
+#pragma unroll
+  for (int l = 0; l < 10; ++l) p[10 * i + l] = a.v[l];
+}
+template <int N>
+NT_HD NT_INLINE void ld_w(uint32_t* w, const uint32_t* p, size_t i) {
+#pragma unroll
+  for (int l = 0; l < N; ++l) w[l] = p[N * i + l];
+}
+template <int N>
+NT_HD NT_INLINE void st_w(uint32_t* p, size_t i, const uint32_t* w) {
+#pragma unroll
+  for (int l = 0; l < N; ++l) p[N * i + l] = w[l];
+}
+
+NT_HD NT_INLINE void item_fe_mul(size_t i, const uint32_t* f, const uint32_t* g, uint32_t* out) {
+  fe a, b, c;
+  ld_fe(a, f, i);
+  ld_fe(b, g, i);
+  fe_mul(c, a, b);
+  st_fe(out, i, c);
+}
+NT_HD NT_INLINE void item_fe_sq(size_t i, const uint32_t* f, uint32_t* out) {
+  fe a, c;
+  ld_fe(a, f, i);
+  fe_sq(c, a);
+  st_fe(out, i, c);
+}
+NT_HD NT_INLINE void item_fe_sq_wide(size_t i, const uint32_t* f, uint32_t* out) {
+  fe a, c;
+  ld_fe(a, f, i);
+  fe_sq_wide(c, a);
+  st_fe(out, i, c);
+}
+NT_HD NT_INLINE void item_fe_carry(size_t i, const uint32_t* f, uint32_t* out) {
+  fe a;
+  ld_fe(a, f, i);
+  fe_carry(a);
+  st_fe(out, i, a);
+}
+NT_HD NT_INLINE void item_fe_tobytes(size_t i, const uint32_t* f, uint32_t* out8) {
+  fe a;
+  ld_fe(a, f, i);
+  uint32_t w[8];
+  fe_tobytes_w(w, a);
+  st_w<8>(out8, i, w);
+}
+NT_HD NT_INLINE void item_fe_frombytes(size_t i, const uint32_t* in8, uint32_t* out) {
+  uint32_t w[8];
+  ld_w<8>(w, in8, i);
+  fe a;
+  fe_frombytes_w(a, w);
+  st_fe(out, i, a);
+}
+// vt: fe_invert_vt (binary GCD), else fe_invert (Fermat); canonical words out
+NT_HD NT_INLINE void item_fe_invert(size_t i, const uint32_t* f, uint32_t* out8, int vt) {
+  fe a, r;
+  ld_fe(a, f, i);
+  if (vt) fe_invert_vt(r, a);
+  else fe_invert(r, a);
+  uint32_t w[8];
+  fe_tobytes_w(w, r);
+  st_w<8>(out8, i, w);
+}
+NT_HD NT_INLINE void item_sc_reduce512(size_t i, const uint32_t* in16, uint32_t* out8) {
+  uint32_t x[16], r[8];
+  ld_w<16>(x, in16, i);
+  sc_reduce512(r, x);
+  st_w<8>(out8, i, r);
+}
+NT_HD NT_INLINE void item_sc_muladd(size_t i, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                                    uint32_t* out8) {
+  uint32_t wa[8], wb[8], wc[8], r[8];
+  ld_w<8>(wa, a, i);
+  ld_w<8>(wb, b, i);
+  ld_w<8>(wc, c, i);
+  sc_muladd(r, wa, wb, wc);
+  st_w<8>(out8, i, r);
+}
+NT_HD NT_INLINE void item_sc_mul(size_t i, const uint32_t* a, const uint32_t* b, uint32_t* out8) {
+  uint32_t wa[8], wb[8], r[8];
+  ld_w<8>(wa, a, i);
+  ld_w<8>(wb, b, i);
+  sc_mul(r, wa, wb);
+  st_w<8>(out8, i, r);
+}
+// out8 = |k'|, neg[i] = 1 iff k' = k - L was taken
+NT_HD NT_INLINE void item_sc_reduce_half(size_t i, const uint32_t* k8, uint32_t* out8, uint32_t* neg) {
+  uint32_t k[8];
+  ld_w<8>(k, k8, i);
+  neg[i] = sc_reduce_half(k);
+  st_w<8>(out8, i, k);
+}
+NT_HD NT_INLINE void item_sc_recode_w4(size_t i, const uint32_t* s8, uint32_t* out8) {
+  uint32_t s[8], d[8];
+  ld_w<8>(s, s8, i);
+  sc_recode_w4(d, s);
+  st_w<8>(out8, i, d);
+}
+NT_HD NT_INLINE void item_sc_is_canonical(size_t i, const uint32_t* s8, uint32_t* out1) {
+  uint32_t s[8];
+  ld_w<8>(s, s8, i);
+  out1[i] = sc_is_canonical(s);
+}
+// sc_halfsize_t<lehmer>: u, v (8 words), sign of u, bits
+NT_HD NT_INLINE void item_sc_halfsize(size_t i, const uint32_t* k8, uint32_t* u8, uint32_t* uneg, uint32_t* v8,
+                                      int32_t* bits, int lehmer) {
+  uint32_t k[8], u[8], v[8], un;
+  ld_w<8>(k, k8, i);
+  bits[i] = lehmer ? sc_halfsize_t<true>(u, un, v, k) : sc_halfsize_t<false>(u, un, v, k);
+  uneg[i] = un;
+  st_w<8>(u8, i, u);
+  st_w<8>(v8, i, v);
+}
+// k = H(R || A || M) mod L, M = msg[off[i] .. off[i] + len[i]) at whatever alignment that is
+NT_HD NT_INLINE void item_hram(size_t i, const uint32_t* R8, const uint32_t* A8, const uint8_t* msg,
+                               const uint64_t* off, const uint64_t* len, uint32_t* out8, int fast) {
+  uint32_t R[8], A[8], k[8];
+  ld_w<8>(R, R8, i);
+  ld_w<8>(A, A8, i);
+  if (fast) hram_scalar<true>(k, R, A, msg + off[i], len[i]);
+  else hram_scalar<false>(k, R, A, msg + off[i], len[i]);
+  st_w<8>(out8, i, k);
+}
+// out4 = decodes, [8]P == 0 by doublings, torsion-y compare of the decoded point,
+// torsion_y_words on the canonical y of the encoding
+NT_HD NT_INLINE void item_point_checks(size_t i, const uint32_t* enc8, uint32_t* out4) {
+  uint32_t w[8], y[8];
+  ld_w<8>(w, enc8, i);
+  ge_p3 P;
+  out4[4 * i] = ge_frombytes_w(P, w);
+  out4[4 * i + 1] = ge_is_small_order(P);
+  out4[4 * i + 2] = ge_is_small_order_affine(P);
+  fe_tobytes_w(y, P.Y);
+  out4[4 * i + 3] = torsion_y_words(y);
+}
+// verify_uv's variable-base part: -[u]A - [v]R through the lane's tables, every
+// lane of a wave running its wave's largest window count; out8 = the encoding
+template <class ATab>
+NT_HD NT_INLINE void item_ladder_uv(size_t i, const uint32_t* A8, const uint32_t* R8, const uint32_t* u8,
+                                    const uint32_t* uneg, const uint32_t* v8, const int32_t* bits, ATab& at,
+                                    uint32_t* out8, bool write) {
+  uint32_t Aw[8], Rw[8], u[8], v[8], ud[8], vd[8], o[8];
+  ld_w<8>(Aw, A8, i);
+  ld_w<8>(Rw, R8, i);
+  ld_w<8>(u, u8, i);
+  ld_w<8>(v, v8, i);
+  {
+    ge_p3 A;
+    ge_frombytes_w(A, Aw);
+    ptab_build(A, uneg[i] ^ 1u, at, 0);
+  }
+  {
+    ge_p3 R;
+    ge_frombytes_w(R, Rw);
+    ptab_build(R, 1u, at, kTabR);
+  }
+  sc_recode_w4(ud, u);
+  sc_recode_w4(vd, v);
+  const int W = wave_max((bits[i] + 5) >> 2);
+  ge_cp t;
+  ladder_ar(t, ud, vd, W, at);
+  ge_p2 p;
+  ge_cp_to_p2(p, t);
+  ge_tobytes_w(o, p);
+  if (write) st_w<8>(out8, i, o);
+}
+
+}  // namespace ntp

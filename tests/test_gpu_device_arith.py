@@ -1,0 +1,84 @@
+"""The edge-case checks of the Ed25519 arithmetic (tests/_arith_checks.py) on the
+code the GPU executes: the gfx950 build of narwhal-tusk_amd/csrc/*.hpp behind the
+device probe (tests/cpp/nt_device_probe.hip).  The other GPU tests only see a
+signature's accept/reject bit, and every scalar they reach is a SHA-512 output;
+here the device functions get the inputs that stress them directly -- limbs at
+their bounds, chosen wave compositions for the wave-level exits (fe_invert_vt,
+wave_max), scalars with huge partial quotients through the v_rcp_f64 Lehmer
+quotient, messages at every byte alignment.  tests/test_host_arith.py runs the
+same checks on the host build.  Nothing is compiled here: a missing or stale
+probe library fails at once.
+"""
+import glob
+import os
+
+import pytest
+
+import _arith_checks as C
+import _devprobe
+import _hostarith as H
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return _devprobe.runner()
+
+
+@pytest.fixture(scope="module")
+def host():
+    """the host build as build() left it (the half-size reference and the ladder's vectors)"""
+    lib = os.path.join(H.CPP, "build", "libnthost.so")
+    srcs = [os.path.join(H.CPP, "nt_host_harness.cpp"), os.path.join(H.CPP, "nt_probe_items.hpp")] + \
+        glob.glob(os.path.join(_devprobe.CSRC, "*.hpp"))
+    _devprobe.check_fresh(lib, srcs)
+    return H.runner("", build=False)
+
+
+def test_fe_mul_at_bounds(dev):
+    C.check_fe_mul_bounds(dev)
+
+
+def test_fe_sq_at_bounds(dev):
+    C.check_fe_sq_bounds(dev)
+
+
+def test_fe_bytes(dev):
+    C.check_fe_bytes(dev)
+
+
+def test_inversion_wave_compositions(dev):
+    C.check_inversion(dev)
+
+
+def test_sc_reduce512(dev):
+    C.check_sc_reduce512(dev)
+
+
+def test_sc_muladd_mul_canonical(dev):
+    C.check_sc_mul(dev)
+
+
+def test_sc_reduce_half(dev):
+    C.check_sc_reduce_half(dev)
+
+
+def test_sc_recode_w4(dev):
+    C.check_sc_recode_w4(dev)
+
+
+def test_halfsize_on_device_reciprocal(dev, host):
+    C.check_halfsize(dev, host.sc_halfsize(C.halfsize_scalars(), 0))
+
+
+def test_hram_every_alignment(dev):
+    C.check_hram(dev)
+
+
+def test_point_decoding_and_small_order(dev):
+    C.check_point_checks(dev)
+
+
+def test_ladder_lane_mixed_window_counts(dev, host):
+    C.check_ladder(dev, H.host_halfsize)

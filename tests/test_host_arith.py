@@ -13,79 +13,97 @@ import random
 import numpy as np
 import pytest
 
+import _arith_checks as C
 import _hostarith as H
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-M26, M25 = (1 << 26) - 1, (1 << 25) - 1
-
-# largest limbs the formulas in ge25519.hpp can feed into mul/sq (see fe25519.hpp header)
-F_MAX = [0xFFFFFB4 + 0x8000000 if i == 0 else (0xFFFFFFC + 0x8000000 if i % 2 == 0 else 0x7FFFFFC + 0x4000000)
-         for i in range(10)]                                   # fe_sub4 of (2x reduced) -> f side only
-G_MAX = [0x7FFFFDA + 0x4000000 if i == 0 else (0x7FFFFFE + 0x4000000 if i % 2 == 0 else 0x3FFFFFE + 0x2000000 + (1 << 18))
-         for i in range(10)]                                   # fe_sub of reduced -> either side
-S_MAX = [2 * M26 if i % 2 == 0 else 2 * M25 + (1 << 18) for i in range(10)]  # sum of two reduced -> sq_wide input
-# fe_sq contract: even limbs < 2^26.1, odd < 2^25.1 (reduced outputs, d y^2 + 1)
-R_MAX = [int(2 ** 26.1) - 1 if i % 2 == 0 else int(2 ** 25.1) - 1 for i in range(10)]
 
 
-def _is_reduced(limbs):
-    return all(l <= (M26 if i % 2 == 0 else M25 + (1 << 19)) for i, l in enumerate(limbs))
+@pytest.fixture(scope="module")
+def host():
+    return H.runner("")
 
 
-def _rand_limbs(rng, mx):
-    return [rng.randint(0, m) for m in mx]
+# The checks of tests/_arith_checks.py take a runner: here the host build of the
+# headers, in tests/test_gpu_device_arith.py the gfx950 build behind the device probe.
+def test_fe_mul_extreme_bounds(host):
+    C.check_fe_mul_bounds(host)
 
 
-def test_fe_mul_extreme_bounds():
-    rng = random.Random(1)
-    cases = [(F_MAX, G_MAX), (F_MAX, F_MAX[:0] + [min(a, b) for a, b in zip(G_MAX, G_MAX)])]
-    for _ in range(3000):
-        cases.append((_rand_limbs(rng, F_MAX), _rand_limbs(rng, G_MAX)))
-    for k in range(10):  # single-limb maxima
-        f = [0] * 10
-        f[k] = F_MAX[k]
-        cases.append((f, G_MAX))
-    for f, g in cases:
-        out = H.fe_mul(f, g)
-        assert H.value(out) % H.P == H.value(f) * H.value(g) % H.P
-        assert _is_reduced(out), out
+def test_fe_sq_extreme_bounds(host):
+    C.check_fe_sq_bounds(host)
 
 
-def test_fe_sq_extreme_bounds():
-    rng = random.Random(2)
-    for sq, mx in ((H.fe_sq, R_MAX), (H.fe_sq_wide, S_MAX)):
-        cases = [mx] + [_rand_limbs(rng, mx) for _ in range(3000)]
-        for k in range(10):  # single-limb maxima
-            f = [0] * 10
-            f[k] = mx[k]
-            cases.append(f)
-        for f in cases:
-            out = sq(f)
-            assert H.value(out) % H.P == H.value(f) ** 2 % H.P
-            assert _is_reduced(out)
+def test_fe_tobytes_canonical(host):
+    C.check_fe_bytes(host)
 
 
-def test_fe_tobytes_canonical():
-    vals = [0, 1, H.P - 1, H.P, H.P + 1, H.P + 18, 2 ** 255 - 1, 2 ** 255 - 20, 19, 2 ** 254]
-    rng = random.Random(3)
-    vals += [rng.randrange(0, 2 ** 255) for _ in range(500)]
-    for v in vals:
-        limbs = H.to_limbs(v)
-        assert H.fe_tobytes(limbs) == (v % H.P).to_bytes(32, "little")
-    # unreduced limb patterns (carry input) also canonicalize
-    for _ in range(500):
-        limbs = _rand_limbs(rng, G_MAX)
-        assert H.fe_tobytes(limbs) == (H.value(limbs) % H.P).to_bytes(32, "little")
+def test_sc_reduce512(host):
+    C.check_sc_reduce512(host)
 
 
-def test_sc_reduce512():
-    rng = random.Random(4)
-    for _ in range(2000):
-        x = rng.randrange(0, 2 ** 512)
-        assert H.sc_reduce512(x.to_bytes(64, "little")) == (x % H.L).to_bytes(32, "little")
-    for x in (0, H.L - 1, H.L, H.L + 1, 2 ** 512 - 1, H.L * (2 ** 259)):
-        x %= 2 ** 512
-        assert H.sc_reduce512(x.to_bytes(64, "little")) == (x % H.L).to_bytes(32, "little")
+def test_sc_muladd_mul_canonical(host):
+    C.check_sc_mul(host)
+
+
+def test_sc_reduce_half(host):
+    C.check_sc_reduce_half(host)
+
+
+def test_sc_recode_w4(host):
+    C.check_sc_recode_w4(host)
+
+
+def test_hram_every_alignment(host):
+    C.check_hram(host)
+
+
+def test_point_decoding_and_small_order(host):
+    C.check_point_checks(host)
+
+
+@pytest.mark.parametrize("variant", ["", "_fullgcd"])
+def test_inversion_wave_compositions(variant):
+    """default build: the loop is left per value once a = 0; _fullgcd
+    (-DNT_GCD_EARLY_EXIT=0): all 17 outer iterations for every value, which is what
+    a GPU lane runs whose wave still has work (iterations with a = 0)"""
+    C.check_inversion(H.runner(variant))
+
+
+def test_inversion_inputs_take_the_negation_branch():
+    """gcd_lincomb_shift negates a negative matrix row about once in 3,000
+    inversions; the inputs of the inversion check must reach that branch"""
+    vals, _ = C.inversion_inputs()
+    counts = [H.gcd_neg_count(C.to_limbs(v)) for v in vals]
+    assert min(counts) >= 0  # -1: the harness's restated loop no longer ends in a = 0, b = 1
+    took = sum(c > 0 for c in counts)
+    print("inversion inputs that negate a row: %d of %d" % (took, len(vals)))
+    assert took >= 3
+
+
+@pytest.mark.parametrize("variant", ["", "_rcp"])
+def test_halfsize_twin(variant):
+    """default build: exact quotients floor(a / b); _rcp: floor(a * r) with r = 1 / b
+    off by up to 2 ulp (NT_LAT_RCP_MODEL, a model of the device's v_rcp_f64), so the
+    quotient corrections of lat_lehmer_batch run; both must equal the default
+    build's one-step loop"""
+    C.check_halfsize(H.runner(variant), H.runner("").sc_halfsize(C.halfsize_scalars(), 0))
+
+
+def test_ladder_lane_mixed_window_counts(host):
+    C.check_ladder(host, H.host_halfsize)
+
+
+def test_device_probe_exports_every_entry():
+    """tests/cpp/build/libntprobe.so (the gfx950 build of the same item functions)
+    exports one ntp_* entry point per check; loading it needs no GPU"""
+    import subprocess
+    import _devprobe
+    subprocess.run(["make", "-s", "-C", H.CPP, "build/libntprobe.so"], check=True)
+    lib = _devprobe.load()
+    for sym in _devprobe.EXPORTS:
+        getattr(lib, sym)
+    assert len(_devprobe.EXPORTS) == 17
 
 
 def test_sha512_host_build():
@@ -394,3 +412,20 @@ def test_opcount_matches_committed_profile():
     cur = mod.measure()
     for key in ("verify_strict_fe_mul", "verify_strict_fe_sq", "verify_strict_mads"):
         assert cur[key] == committed[key], key
+
+
+def test_device_probe_refuses_a_missing_or_stale_library(tmp_path):
+    """the GPU tests never compile: a probe library that is missing or older than
+    one of its sources raises (a failure, not a skip) and names the file"""
+    import _devprobe
+    lib, src = tmp_path / "libx.so", tmp_path / "x.hpp"
+    src.write_text("")
+    with pytest.raises(RuntimeError, match="missing"):
+        _devprobe.check_fresh(str(lib), [str(src)])
+    lib.write_text("")
+    os.utime(src, (1000, 1000))
+    os.utime(lib, (2000, 2000))
+    _devprobe.check_fresh(str(lib), [str(src)])
+    os.utime(src, (3000, 3000))
+    with pytest.raises(RuntimeError, match="older than"):
+        _devprobe.check_fresh(str(lib), [str(src)])
