@@ -1,7 +1,7 @@
 // key_table.hpp -- the host-side index of the key registry (host-only; shared by
-// ntcrypto.cpp and the host test harness).
+// verify.cpp, groups.cpp and the host test harness).
 //
-// The registry (ntcrypto.cpp, include/ntcrypto.h nt_set_key_cache) keeps the
+// The registry (registry.cpp, include/ntcrypto.h nt_set_key_cache) keeps the
 // committee key cache behind the unchanged entry points: nt_ed25519_verify_strict
 // and nt_ed25519_verify_batch_groups carry raw 32-byte keys (the crate's
 // `PublicKey`, crypto/src/lib.rs:65-119), and every call maps each key to its

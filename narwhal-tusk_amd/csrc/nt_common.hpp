@@ -38,7 +38,7 @@ constexpr int kKeyCombNarrow = 16;  // 16 additions, 67 MB per key
 
 // Digit widths of the comb of the base point B (one per device ordinal): 24 bits
 // by measurement, 20 bits when the context's HBM budget or the
-// device's free memory cannot hold 11.8 GB (ntcrypto.cpp: comb_b_for).  Every
+// device's free memory cannot hold 11.8 GB (context.cpp: comb_b_for).  Every
 // kernel that reads it is compiled for both; the launchers dispatch on the width
 // of the comb the device entry holds.
 #ifndef NT_BCOMB_WIDE

@@ -1,5 +1,5 @@
 // pipe_plan.hpp -- chunk plans of the host entry points' copy / kernel
-// pipeline (host-only arithmetic, shared by ntcrypto.cpp and the host test
+// pipeline (host-only arithmetic, shared by pipeline.hpp and the host test
 // harness).  Every boundary but the end is a multiple of 64
 // items, so each chunk owns whole 64-bit verdict words.
 #pragma once
@@ -12,6 +12,18 @@
 namespace nt {
 
 constexpr int kMaxChunks = 16;  // chunk events per execution slot (runtime.hpp cev)
+
+// verdict bit i of 64-bit words (the kernels' output) and of an LSB-first byte bitmap (the ABI's)
+inline bool word_bit(const uint64_t* w, uint64_t i) { return (w[i >> 6] >> (i & 63)) & 1; }
+inline void word_put(uint64_t* w, uint64_t i, bool v) {
+  if (v) w[i >> 6] |= 1ull << (i & 63);
+  else w[i >> 6] &= ~(1ull << (i & 63));
+}
+inline bool byte_bit(const uint8_t* b, uint64_t i) { return (b[i >> 3] >> (i & 7)) & 1; }
+inline void byte_put(uint8_t* b, uint64_t i, bool v) {
+  if (v) b[i >> 3] |= (uint8_t)(1u << (i & 7));
+  else b[i >> 3] &= (uint8_t)~(1u << (i & 7));
+}
 
 // Chunks of a host verify call (one round R1 = the signatures one wave of
 // resident waves covers at ONE signature per lane).  The call is PCIe-bound --
@@ -103,6 +115,17 @@ inline std::vector<uint64_t> chunk_targets(uint64_t total, uint64_t R, uint64_t 
   }
   t.push_back(left);
   return t;
+}
+
+// consecutive item ranges [a, b) of the given sizes, from 0
+inline std::vector<std::pair<uint64_t, uint64_t>> plan_chunks(const std::vector<uint64_t>& targets) {
+  std::vector<std::pair<uint64_t, uint64_t>> r;
+  uint64_t a = 0;
+  for (uint64_t t : targets) {
+    r.emplace_back(a, a + t);
+    a += t;
+  }
+  return r;
 }
 
 // Certificate groups [glo, ghi) -> chunks [g0, g1) holding about targets[c]

@@ -1,6 +1,8 @@
 // runtime.hpp -- the host runtime's internal types, shared by the C-ABI
-// translation units (ntcrypto.cpp: hashing / verification / key cache;
-// ingest_gpu.cpp: wire ingestion on the device).  Not part of the ABI.
+// translation units (context.cpp, calibrate.cpp, verify.cpp, groups.cpp,
+// keyset.cpp, sign.cpp, dev_api.cpp: one per family of entry points;
+// registry.cpp: the key registry; ingest_gpu.cpp: wire ingestion on the
+// device).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -73,7 +75,7 @@ struct HostBuf {
   T* as() const { return (T*)p; }
 };
 
-// nt_host_alloc registry: [base, base + bytes) of every live pinned buffer (ntcrypto.cpp)
+// nt_host_alloc registry: [base, base + bytes) of every live pinned buffer (context.cpp)
 extern std::mutex g_pin_mu;
 extern std::map<uintptr_t, uint64_t> g_pinned;
 bool is_pinned(const void* p, uint64_t bytes);
@@ -86,7 +88,7 @@ enum { B_DATA, B_OFF, B_LEN, B_PK, B_SIG, B_OUT, B_OUT2, B_FIRST, B_CNT, B_STASH
 // -- repeated ordinals, a second Backend, the contention probe's contexts;
 // ADVICE r02).  Built by the first verify / sign call that needs it (never at
 // nt_init: a digest-only worker pays nothing), freed with the last user
-// (ntcrypto.cpp: shared_comb_b, comb_b_for).
+// (context.cpp: shared_comb_b, comb_b_for).
 struct CombB {
   int ordinal = -1;
   int bits = 0;
@@ -99,7 +101,7 @@ struct CombB {
 };
 struct Device;
 std::shared_ptr<CombB> shared_comb_b(Device& dv, int bits, int& rc);
-// the comb of B of a slot (created by its entry on first use; ntcrypto.cpp)
+// the comb of B of a slot (created by its entry on first use; context.cpp)
 int comb_b_for(Device& dv);
 
 // The context's HBM budget on one device entry (shared by its execution slots
@@ -177,7 +179,7 @@ struct Device {
   hipEvent_t stash_done = nullptr;  // same for the key-cache stash d[B_STASH] (host and device API)
   // host entry points: chunk c's H2D copies go on cstream, cev[c] marks them
   // done, and the host launches chunk c's kernels once it has waited for cev[c]
-  // (ntcrypto.cpp run_chunks), so copies of chunk c+1 overlap kernels of chunk c
+  // (pipeline.hpp run_chunks), so copies of chunk c+1 overlap kernels of chunk c
   hipStream_t cstream = nullptr;
   hipEvent_t cev[16] = {};
   // ... and chunks alternate between two compute streams, so the waves of chunk
@@ -478,7 +480,7 @@ std::shared_ptr<const RegSnap> reg_snapshot(nt_ctx* ctx);
 constexpr uint32_t kRegNoteMax = 256;
 void reg_note_misses(nt_ctx* ctx, const std::vector<const uint8_t*>& keys);
 void reg_count(nt_ctx* ctx, uint64_t hits, uint64_t misses);
-// first-use tables and width choice shared with nt_keyset_create (ntcrypto.cpp)
+// first-use tables and width choice shared with nt_keyset_create (context.cpp)
 int keyset_comb_bits(nt_ctx* ctx, uint32_t nkeys);
 hipError_t table_malloc(void** p, size_t bytes);  // comb tables (NT_TABLE_ALLOC)
 int comb_b_for(Device& dv);
@@ -585,6 +587,28 @@ int run_sharded(nt_ctx* ctx, uint64_t n, uint64_t align, F&& fn, bool latency = 
     int _rc = (expr);             \
     if (_rc != NT_OK) return _rc; \
   } while (0)
+
+// ---- what the translation units share besides the types above ----
+// context.cpp: everything the verify kernel of slot dv reads besides its inputs; device entry `dev` or null
+int verify_tables(Device& dv);
+Device* dev_of(nt_ctx* ctx, int dev);
+// context.cpp, the small-call path (cpu_lane.hpp): NT_SMALL_* overrides of single
+// model fields, the host threads of a call of `items` items, and whether the host lane takes
+// a verify call (kind: nt::kRouteUncached / kRouteKeyCache) or a digest call
+NtSmallModel small_model_with_env(NtSmallModel m);
+int small_threads(const nt_ctx* ctx, uint64_t items);
+bool small_verify(nt_ctx* ctx, uint64_t nsig, int kind = nt::kRouteUncached);
+bool small_sha(nt_ctx* ctx, uint64_t n, const uint64_t* len);
+int calibrate_small(nt_ctx* ctx);  // calibrate.cpp
+// verify.cpp: the GPU bodies of nt_ed25519_verify_strict (no registry) and nt_ed25519_verify_keyset
+int verify_strict_gpu(nt_ctx* ctx, const uint8_t* pk32, const uint8_t* sig64, const uint8_t* msg, const uint64_t* off,
+                      const uint64_t* len, uint64_t n, uint8_t* out_bitmap);
+int verify_keyset_gpu(nt_ctx* ctx, const KeyDev& kd, int mode, const uint32_t* key_idx, const uint8_t* sig64,
+                      const uint8_t* msg, const uint64_t* off, const uint64_t* len, uint64_t n, uint8_t* out_bitmap);
+// keyset.cpp: nt_keyset_create at a given key-comb width (0 = the widest that fits); the key
+// encoding and check mode of one key-cache entry on the small-call path (-1: no such key)
+int keyset_create(nt_ctx* ctx, const uint8_t* pk32, uint32_t nkeys, int bits, nt_keyset** out);
+int keyset_key(const nt_keyset* ks, int mode, uint32_t kraw, uint8_t A[32]);
 
 
 }  // namespace ntrt

@@ -1,5 +1,5 @@
 // small_model.hpp -- the small-call path's cost model and routing rules
-// (host-only; shared by ntcrypto.cpp and the host test harness, so the routing
+// (host-only; shared by context.cpp and the host test harness, so the routing
 // decision is tested on the CPU: tests/test_small_route.py).
 //
 // The reference calls the hot path one message at a time (Core::run,
@@ -17,7 +17,7 @@
 #include <cmath>
 
 // Calibrated by nt_set_small_call_path on the context's own host threads and
-// device (ntcrypto.cpp calibrate_small); NT_SMALL_* environment variables
+// device (calibrate.cpp calibrate_small); NT_SMALL_* environment variables
 // override single fields.  The defaults are round-2 / round-6 measurements.
 struct NtSmallModel {
   double cpu_verify_us = 36.0;    // one host-lane verify_strict on one thread

@@ -32,6 +32,7 @@ inline double nth_rcp_model(double b) {
 #include "../../narwhal-tusk_amd/csrc/fe_inv_vt.hpp"
 #include "../../narwhal-tusk_amd/csrc/ks_plan.hpp"
 #include "../../narwhal-tusk_amd/csrc/pipe_plan.hpp"
+#include "../../narwhal-tusk_amd/csrc/group_plan.hpp"
 #include "../../narwhal-tusk_amd/csrc/key_table.hpp"
 #include "../../narwhal-tusk_amd/csrc/small_model.hpp"
 #include "nt_probe_items.hpp"
@@ -515,6 +516,57 @@ int nth_plan_group_chunks(unsigned long long G, const uint32_t* cnt, const unsig
   const auto r = plan_group_chunks(0, G, cnt, tg);
   for (size_t i = 0; i < r.size() && (int)i < maxn; ++i) out[i] = r[i].second;
   return (int)r.size();
+}
+// One shard of a groups call (group_plan.hpp): groups [glo, ghi) of first / cnt.  ends / E / W
+// take the chunks' end groups and C + 1 signature and word bases (at most maxn chunks), start the
+// ghi - glo chunk-local group starts, scal = m, sw, gw, max_chunk, direct; returns the chunk count
+int nth_group_plan(unsigned long long glo, unsigned long long ghi, const uint64_t* first, const uint32_t* cnt,
+                   const unsigned long long* targets, int nt, uint64_t* ends, uint64_t* E, uint64_t* W,
+                   uint64_t* start, uint64_t* scal, int maxn) {
+  const GroupShard p = plan_group_shard(glo, ghi, first, cnt, std::vector<uint64_t>(targets, targets + nt), start);
+  p.fill_starts(cnt);
+  for (size_t c = 0; c < p.chunks() && (int)c < maxn; ++c) {
+    ends[c] = p.ch[c].second;
+    E[c + 1] = p.E[c + 1];
+    W[c + 1] = p.W[c + 1];
+  }
+  E[0] = W[0] = 0;
+  const uint64_t s[5] = {p.m, p.sw, p.gw, p.max_chunk, (uint64_t)p.direct};
+  std::memcpy(scal, s, sizeof s);
+  return (int)p.chunks();
+}
+// the verdict bit of every signature of the shard, in group order (m entries)
+void nth_group_bits(unsigned long long glo, unsigned long long ghi, const uint64_t* first, const uint32_t* cnt,
+                    const unsigned long long* targets, int nt, uint64_t* bits) {
+  std::vector<uint64_t> start(ghi - glo + 1);
+  const GroupShard p = plan_group_shard(glo, ghi, first, cnt, std::vector<uint64_t>(targets, targets + nt), start.data());
+  p.fill_starts(cnt);
+  for (size_t c = 0; c < p.chunks(); ++c)
+    for (uint64_t g = p.ch[c].first; g < p.ch[c].second; ++g)
+      for (uint32_t t = 0; t < cnt[g]; ++t) *bits++ = p.bit(c, g, t);
+}
+// M misses (group, index within the group) with the fallback kernel's verdict words mw merged into sbits / gbits
+void nth_group_merge(unsigned long long glo, unsigned long long ghi, const uint64_t* first, const uint32_t* cnt,
+                     const unsigned long long* targets, int nt, const uint64_t* miss_g, const uint32_t* miss_t,
+                     unsigned long long M, const uint64_t* mw, uint64_t* sbits, uint64_t* gbits) {
+  std::vector<uint64_t> start(ghi - glo + 1);
+  const GroupShard p = plan_group_shard(glo, ghi, first, cnt, std::vector<uint64_t>(targets, targets + nt), start.data());
+  p.fill_starts(cnt);
+  std::vector<GroupMiss> miss;
+  for (unsigned long long j = 0; j < M; ++j) {
+    uint32_t c = 0;
+    while (miss_g[j] >= p.ch[c].second) ++c;
+    miss.push_back(GroupMiss{miss_g[j], c, miss_t[j]});
+  }
+  merge_group_misses(p, cnt, miss, mw, sbits, gbits);
+}
+// the shard's signature verdict words scattered into the caller's byte bitmap
+void nth_group_scatter(unsigned long long glo, unsigned long long ghi, const uint64_t* first, const uint32_t* cnt,
+                       const unsigned long long* targets, int nt, const uint64_t* sbits, uint8_t* out) {
+  std::vector<uint64_t> start(ghi - glo + 1);
+  const GroupShard p = plan_group_shard(glo, ghi, first, cnt, std::vector<uint64_t>(targets, targets + nt), start.data());
+  p.fill_starts(cnt);
+  scatter_sig_bits(p, first, cnt, sbits, out);
 }
 // streamed rows (ks_stream_plan): out = waves, rows, prow, per_simd
 void nth_ks_stream_plan(unsigned long long n, uint32_t cus, uint32_t cap, int force, uint32_t* out) {
