@@ -315,6 +315,14 @@ void nt_host_free(void *p);
  * counted).  So an offset read before its producer wrote it (round 4's fault
  * r04e: a wild offset from a cross-stream race) cannot fault the card.
  *
+ * The uncached verify kernel (nt_dev_ed25519_verify, the host entry points'
+ * chunks) keeps the decompressed x of the public keys it has seen in a table
+ * per device entry (NT_XCACHE_SLOTS slots of 32 bytes, default 2^21; 0 = off;
+ * counted against the HBM budget) and checks a kept x instead of taking the
+ * square root again.  Verdicts do not depend on the table -- an entry is used
+ * only when it is proven to be the key's x -- and rates do: a batch whose keys
+ * this context has verified before runs about 6 % faster.
+ *
  * nt_dev_stream returns device entry `dev`'s two compute streams (which = 0 /
  * 1), the streams the host entry points pipeline on: non-blocking, ordered
  * against no other stream (NT_STREAMS=mask: each on a hardware queue of its

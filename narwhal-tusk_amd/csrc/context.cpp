@@ -139,9 +139,46 @@ int comb_b_for(Device& dv) {
   return NT_OK;
 }
 
+// The x cache of execution slot dv: its entry's, allocated by the entry's first verify that finds
+// NT_XCACHE_SLOTS non-zero, at that many slots (default 2^21 = 64 MB; rounded down to a power of two),
+// zero-filled, and reserved in the entry's HBM budget.  A table that does not fit the budget or
+// the device is skipped silently: the kernel then decompresses every key as before.
+static void xcache_for(Device& dv) {
+  if (dv.xtab_ready.load(std::memory_order_acquire)) return;
+  Device& e = *dv.entry;
+  std::lock_guard<std::mutex> lk(e.tables_mu);
+  if (!e.xtab_tried) {
+    unsigned long long want = nt::kXCacheSlotsDefault;
+    if (const char* v = std::getenv("NT_XCACHE_SLOTS")) want = std::strtoull(v, nullptr, 10);
+    const uint32_t slots = nt::xcache_slots_pow2(want, nt::kXCacheSlotsMax);
+    if (!slots) return;  // off for this launch: the first one that asks for a table allocates it
+    e.xtab_tried = true;
+    const uint64_t bytes = 32ull * slots;
+    if (e.budget->reserve_aux(bytes)) {
+      void* p = nullptr;
+      if (hipSetDevice(e.ordinal) == hipSuccess && hipMalloc(&p, bytes) == hipSuccess &&
+          hipMemsetAsync(p, 0, bytes, dv.stream) == hipSuccess && hipStreamSynchronize(dv.stream) == hipSuccess) {
+        e.d_xtab = p;
+        e.xslots = slots;
+        e.xtab_reserved = bytes;
+      } else {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        e.budget->release_aux(bytes);
+      }
+    }
+  }
+  if (&dv != &e) {
+    dv.d_xtab = e.d_xtab;
+    dv.xslots = e.xslots;
+  }
+  dv.xtab_ready.store(1, std::memory_order_release);
+}
+
 // everything the verify kernel of slot dv reads besides its inputs
 int verify_tables(Device& dv) {
   NT_CHK(comb_b_for(dv));
+  xcache_for(dv);
   return dv.ensure_ws();
 }
 

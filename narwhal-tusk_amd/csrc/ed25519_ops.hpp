@@ -4,6 +4,7 @@
 //   ATab:  store(entry, ge_cached) / load_signed(e0, d, ge_cached&)   j*(-A), j = 0..8, per lane
 //          (load_signed: entry e0 + |d|, negated when d < 0)
 //   WComb: load(pos, idx, ge_niels&)                            idx * 2^(16 pos) * P (wide comb)
+//   XCache: load(slot, words) / store(slot, words)              decompressed x of keys seen before (NoXCache: none)
 //
 // Semantics (restated from ed25519-dalek 1.0.1 /
 // curve25519-dalek 3.x):
@@ -487,17 +488,137 @@ NT_HD NT_INLINE uint32_t enc_matches(const fe& x, const uint32_t a[8], const uin
   return same & (((xw[0] & 1u) == sign) | (xz == 0));
 }
 
+// ---------------------------------------------------------------------------
+// The x cache: a public key's decompressed x, kept across calls in a table of
+// 32-byte slots (the verify kernel: DevXCache, kernels_common.hpp; the host
+// harness: a plain array).  Policy:
+//   XCache::kEnabled         compile-time: false = today's decompression, nothing else emitted
+//   active() / mask()        a table is there / its slot count - 1 (a power of two - 1)
+//   load(i, xw), store(i, xw)  the 8 words of slot i <= mask()
+// The table carries no tags, no locks and no valid bits: whatever a slot holds
+// -- zeros, another key's x, the halves of two writers' stores -- is only a
+// CANDIDATE, taken iff ge_frombytes_x_check proves it to be the x the slow path
+// would compute, and any other content means "compute it", never "reject".  So a
+// verdict cannot depend on the table; only the rate does.
+//
+// Placement.  A wave skips the square root only when ALL its lanes hit, so the
+// table has to hold a working set almost without loss: 1M distinct keys in a
+// direct-mapped table of 2^21 slots leave 21 % of them homeless (no wave would
+// ever hit).  Slots therefore form buckets of kXWays = 4 (one 128-byte line),
+// and a key has two buckets (two hashes of its bytes): the probe checks all 8
+// slots, a store goes to the first empty (all-zero) slot of the emptier bucket
+// -- two-choice placement: 15 keys in 1M homeless at that load -- and, with both
+// buckets full, replaces the slot picked by the key's hash.  The hashes matter
+// only for the rate: keys built to collide evict one another and verify at the
+// slow path's cost plus the probe.
+// ---------------------------------------------------------------------------
+struct NoXCache {
+  static constexpr bool kEnabled = false;
+  NT_HD NT_INLINE bool active() const { return false; }
+  NT_HD NT_INLINE uint32_t mask() const { return 0; }
+  NT_HD NT_INLINE void load(uint32_t, uint32_t*) const {}
+  NT_HD NT_INLINE void store(uint32_t, const uint32_t*) const {}
+};
+
+constexpr uint32_t kXWays = 4;          // slots per bucket
+constexpr uint32_t kXCand = 2 * kXWays;  // slots a probe checks
+
+// multiply-xorshift over the 8 key words
+NT_HD NT_INLINE uint32_t xcache_hash(const uint32_t Aw[8], uint32_t seed) {
+  uint32_t h = seed;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    h = (h ^ Aw[i]) * 0x85ebca6bu;
+    h ^= h >> 15;
+  }
+  h *= 0xc2b2ae35u;
+  return h ^ (h >> 16);
+}
+// first slot of the key's bucket for hash h (tables below kXWays slots: slot 0;
+// xcache_cand then wraps within the table)
+NT_HD NT_INLINE uint32_t xcache_bucket(uint32_t h, uint32_t mask) { return (h & (mask / kXWays)) * kXWays; }
+// candidate c (< kXCand) of a key with buckets b0, b1: always <= mask
+NT_HD NT_INLINE uint32_t xcache_cand(uint32_t b0, uint32_t b1, uint32_t c, uint32_t mask) {
+  return ((c < kXWays ? b0 : b1) | (c & (kXWays - 1))) & mask;
+}
+
+// ge_frombytes_w(A, Aw) through the x cache.  A wave takes the shortcut only
+// when every lane finds its x (the square root's 252 squarings cost a wave the
+// same for one lane as for 64); otherwise the whole wave decompresses as before,
+// and the lanes that found nothing leave their x (when the key decodes and
+// x != 0) for the next call.
+template <class XCache>
+NT_HD NT_INLINE uint32_t ge_frombytes_cached(ge_p3& A, const uint32_t Aw[8], const XCache& xc) {
+  if (!XCache::kEnabled) return ge_frombytes_w(A, Aw);
+  const bool have = xc.active();
+  const uint32_t mask = have ? xc.mask() : 0u;
+  const uint32_t h0 = xcache_hash(Aw, 0x9e3779b9u), h1 = xcache_hash(Aw, 0x7f4a7c15u);
+  const uint32_t b0 = xcache_bucket(h0, mask), b1 = xcache_bucket(h1, mask);
+  uint32_t xw[8];
+  if (have) xc.load(xcache_cand(b0, b1, 0, mask), xw);  // issued first: its latency overlaps u and v
+  fe u, v;
+  ge_frombytes_uv(A, u, v, Aw);
+  fe_0(A.X);
+  constexpr uint32_t kNone = kXWays;
+  uint32_t hit = 0, ok = 1, used0 = 0, used1 = 0, free0 = kNone, free1 = kNone;
+  if (have) {
+#pragma unroll 1
+    for (uint32_t c = 0; c < kXCand; ++c) {
+      // the next candidate's load overlaps this one's check
+      uint32_t nx[8];
+      xc.load(xcache_cand(b0, b1, c + 1 < kXCand ? c + 1 : c, mask), nx);
+      uint32_t nz = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) nz |= xw[i];
+      const uint32_t way = c & (kXWays - 1), empty = nz == 0;
+      if (c < kXWays) {
+        used0 += empty ^ 1u;
+        free0 = (empty && free0 == kNone) ? way : free0;
+      } else {
+        used1 += empty ^ 1u;
+        free1 = (empty && free1 == kNone) ? way : free1;
+      }
+      fe x;
+      const uint32_t m = ge_frombytes_x_check(x, xw, u, v, Aw) & (hit ^ 1u);
+      fe_cmov(A.X, x, m);
+      hit |= m;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) xw[i] = nx[i];
+      if (!wave_any(hit ^ 1u)) break;
+    }
+  }
+  if (wave_any(hit ^ 1u)) {
+    ok = ge_frombytes_x(A, u, v, Aw);
+    if (have && !hit && ok) {
+      fe_tobytes_w(xw, A.X);
+      uint32_t nz = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) nz |= xw[i];
+      if (nz) {
+        const bool full = free0 == kNone && free1 == kNone;
+        const bool second = full ? (h1 >> 31) != 0 : (free0 == kNone || (free1 != kNone && used1 < used0));
+        const uint32_t fr = second ? free1 : free0;
+        const uint32_t way = full ? (h0 >> 29) & (kXWays - 1) : fr;
+        xc.store(xcache_cand(b0, b1, (second ? kXWays : 0u) + way, mask), xw);
+      }
+    }
+  }
+  ge_frombytes_t(A);
+  return ok;
+}
+
 // The check for a given lattice vector (u = (-1)^uneg |u|, v) of k with
 // max(bitlen |u|, bitlen v) <= bits; any valid vector gives the same verdict
 // (verify_one below uses sc_halfsize's; the tests also run the trivial (k, 1)).
-template <int MODE, class ATab, class WComb>
+// xc: the x cache of A (R is fresh in every signature and never probed).
+template <int MODE, class ATab, class WComb, class XCache = NoXCache>
 NT_HD NT_INLINE uint32_t verify_uv(const uint32_t Aw[8], const uint32_t Rw[8], const uint32_t Sw[8],
                                    const uint32_t u[8], uint32_t uneg, const uint32_t v[8], int bits, ATab& at,
-                                   const WComb& wb) {
+                                   const WComb& wb, const XCache& xc = XCache()) {
   uint32_t ok = sc_is_canonical(Sw);
   {
     ge_p3 A;
-    ok &= ge_frombytes_w(A, Aw);
+    ok &= ge_frombytes_cached(A, Aw, xc);
     if (MODE == kStrict) ok &= ge_is_small_order_affine(A) ^ 1u;
     ptab_build(A, uneg ^ 1u, at, 0);  // -[u]A = [|u|](u < 0 ? A : -A)
   }
@@ -525,9 +646,10 @@ NT_HD NT_INLINE uint32_t verify_uv(const uint32_t Aw[8], const uint32_t Rw[8], c
 //            [v s mod L]B - [u]A - [v]R == identity     (= [v]([s]B - [k]A - R))
 // with (u, v) = sc_halfsize(k), k = SHA-512(R || A || M) mod L.  at holds this
 // lane's tables, wb is the wide comb of B.
-template <int MODE, class ATab, class WComb>
+template <int MODE, class ATab, class WComb, class XCache = NoXCache>
 NT_HD NT_INLINE uint32_t verify_one(const uint32_t Aw[8], const uint32_t Rw[8], const uint32_t Sw[8],
-                                    const uint8_t* msg, uint64_t len, ATab& at, const WComb& wb) {
+                                    const uint8_t* msg, uint64_t len, ATab& at, const WComb& wb,
+                                    const XCache& xc = XCache()) {
   uint32_t u[8], v[8], uneg;
   int bits;
   {
@@ -535,14 +657,15 @@ NT_HD NT_INLINE uint32_t verify_one(const uint32_t Aw[8], const uint32_t Rw[8], 
     hram_scalar(k, Rw, Aw, msg, len);
     bits = sc_halfsize(u, uneg, v, k);
   }
-  return verify_uv<MODE>(Aw, Rw, Sw, u, uneg, v, bits, at, wb);
+  return verify_uv<MODE>(Aw, Rw, Sw, u, uneg, v, bits, at, wb, xc);
 }
 
 // N verifications per lane in turn.  A[j] = 8 pk words, sig[j] = 16 words
 // (R || s), msg[j]/len[j] = message; at is this lane's table storage.
-template <int MODE, int N, class ATab, class WComb>
+template <int MODE, int N, class ATab, class WComb, class XCache = NoXCache>
 NT_HD NT_INLINE void verify_n(uint32_t ok[N], const uint32_t* const A[N], const uint32_t* const sig[N],
-                              const uint8_t* const msg[N], const uint64_t len[N], ATab& at, const WComb& wb) {
+                              const uint8_t* const msg[N], const uint64_t len[N], ATab& at, const WComb& wb,
+                              const XCache& xc = XCache()) {
 #pragma unroll 1
   for (int j = 0; j < N; ++j) {
     const uint32_t* sj = pick<N>(sig, j);
@@ -550,7 +673,7 @@ NT_HD NT_INLINE void verify_n(uint32_t ok[N], const uint32_t* const A[N], const 
     ld8(Aw, pick<N>(A, j));
     ld8(Rw, sj);
     ld8(Sw, sj + 8);
-    const uint32_t okj = verify_one<MODE>(Aw, Rw, Sw, pick<N>(msg, j), pick<N>(len, j), at, wb);
+    const uint32_t okj = verify_one<MODE>(Aw, Rw, Sw, pick<N>(msg, j), pick<N>(len, j), at, wb, xc);
 #pragma unroll
     for (int q = 0; q < N; ++q)
       if (q == j) ok[q] = okj;

@@ -228,9 +228,13 @@ NT_HD NT_INLINE uint32_t fe_sqrt_ratio_i(fe& r, const fe& u, const fe& v) {
 }
 
 // CompressedEdwardsY::decompress (dalek semantics: y not reduced/rejected,
-// negative zero accepted).  w = 8 little-endian words of the encoding.
-NT_HD NT_INLINE uint32_t ge_frombytes_w(ge_p3& h, const uint32_t w[8]) {
-  fe u, v, yy, one, d;
+// negative zero accepted), in three steps so that a cached x (XCache,
+// ed25519_ops.hpp) can stand in for the square root.  w = 8 little-endian words
+// of the encoding.
+// Step 1: Y = y, Z = 1, u = y^2 - 1, v = d y^2 + 1 (v != 0 for every y: -1/d is
+// a non-square).
+NT_HD NT_INLINE void ge_frombytes_uv(ge_p3& h, fe& u, fe& v, const uint32_t w[8]) {
+  fe yy, one, d;
   fe_frombytes_w(h.Y, w);
   fe_1(one);
   fe_const(d, kFeD);
@@ -240,12 +244,47 @@ NT_HD NT_INLINE uint32_t ge_frombytes_w(ge_p3& h, const uint32_t w[8]) {
   fe_carry(u);                // u = y^2 - 1
   fe_mul(v, yy, d);
   fe_add(v, v, one);          // v = d y^2 + 1
+}
+// Step 2, the slow path: X = the root of u/v with the encoded sign; returns 1 iff
+// the encoding decodes.
+NT_HD NT_INLINE uint32_t ge_frombytes_x(ge_p3& h, const fe& u, const fe& v, const uint32_t w[8]) {
   const uint32_t ok = fe_sqrt_ratio_i(h.X, u, v);
   fe n;
   fe_neg(n, h.X);
   fe_cmov(h.X, n, w[7] >> 31);
   fe_carry(h.X);
-  fe_mul(h.T, h.X, h.Y);
+  return ok;
+}
+// Step 2, the check of a candidate: xw (8 words, from anywhere; x = its limbs) is the X
+// that ge_frombytes_x computes for this encoding iff it is canonical (< p), non-zero,
+// v x^2 == u, and its parity is the encoded sign.  (v x^2 == u makes u/v the
+// square x^2, so the slow path succeeds with a root +-x; of the two roots of a
+// non-zero square exactly one has the encoded parity.)  x = 0 is left to the slow
+// path: y = +-1 and dalek's "negative zero" never take the shortcut.
+NT_HD NT_INLINE uint32_t ge_frombytes_x_check(fe& x, const uint32_t xw[8], const fe& u, const fe& v,
+                                              const uint32_t w[8]) {
+  uint32_t nz = 0, mid = 0xffffffffu;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) nz |= xw[i];
+#pragma unroll
+  for (int i = 1; i < 7; ++i) mid &= xw[i];
+  // < p = 2^255 - 19
+  const uint32_t canon =
+      (xw[7] < 0x7fffffffu) | ((xw[7] == 0x7fffffffu) & ((mid != 0xffffffffu) | (xw[0] < 0xffffffedu)));
+  fe_frombytes_w(x, xw);
+  fe check;
+  fe_sq(check, x);
+  fe_mul(check, check, v);    // v x^2
+  return (nz != 0) & canon & fe_eq(check, u) & ((xw[0] & 1u) == (w[7] >> 31));
+}
+// Step 3: T = X Y
+NT_HD NT_INLINE void ge_frombytes_t(ge_p3& h) { fe_mul(h.T, h.X, h.Y); }
+
+NT_HD NT_INLINE uint32_t ge_frombytes_w(ge_p3& h, const uint32_t w[8]) {
+  fe u, v;
+  ge_frombytes_uv(h, u, v, w);
+  const uint32_t ok = ge_frombytes_x(h, u, v, w);
+  ge_frombytes_t(h);
   return ok;
 }
 

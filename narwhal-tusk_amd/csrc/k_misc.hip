@@ -439,12 +439,12 @@ int keyset_occupancy() { return keyset_occ(); }
 hipError_t launch_verify(int mode, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
                          uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
                          const uint32_t* d_combB, int bbits, void* d_ws, uint32_t ws_slots, uint64_t* d_out_words,
-                         hipStream_t s, int per_lane) {
+                         hipStream_t s, int per_lane, XTab xt) {
   if (n == 0) return hipSuccess;
   if (!d_combB || !d_ws) return hipErrorInvalidValue;
   const int pl = verify_per_lane_for(per_lane);
   const uint64_t blocks = verify_grid(n, ws_slots, pl);
-#define NT_V_ARGS blocks, d_pk, d_sig, d_msg, msg_bytes, d_off, d_len, n, d_combB, d_ws, d_out_words, s, pl
+#define NT_V_ARGS blocks, d_pk, d_sig, d_msg, msg_bytes, d_off, d_len, n, d_combB, d_ws, d_out_words, s, pl, xt
   if (bbits == kBCombBits)
     return mode == kStrict ? launch_verify_m<kStrict, kBCombBits>(NT_V_ARGS)
                            : launch_verify_m<kCofactorless, kBCombBits>(NT_V_ARGS);

@@ -17,9 +17,11 @@ template <int MODE, int OCC, int WB, int NPER>
 __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify(
     const uint32_t* __restrict__ pk, const uint32_t* __restrict__ sig, const uint8_t* __restrict__ msg,
     uint64_t msg_bytes, const uint64_t* __restrict__ off, const uint64_t* __restrict__ len, uint64_t n,
-    const uint32_t* __restrict__ combB, uint4* __restrict__ ws, unsigned long long* __restrict__ out_bits) {
+    const uint32_t* __restrict__ combB, uint4* __restrict__ ws, unsigned long long* __restrict__ out_bits,
+    uint4* xtab, uint32_t xmask) {
   WsATab at{ws, blockIdx.x};
   const WideComb<WB> wb{combB};
+  const DevXCache xc{xtab, xmask};
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t wofs = 64 * NPER * (uint64_t)(threadIdx.x >> 6);
   for (uint64_t base = (uint64_t)blockIdx.x * NPER * kBlock; base < n;
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify(
       L[j] = ms.len;
     }
     uint32_t ok[NPER];
-    verify_n<MODE, NPER>(ok, A, S, M, L, at, wb);
+    verify_n<MODE, NPER>(ok, A, S, M, L, at, wb, xc);
 #pragma unroll
     for (int j = 0; j < NPER; ++j) {
       const unsigned long long bal = __ballot(ok[j] & act[j]);
@@ -56,12 +58,13 @@ __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify(
 template <int MODE, int WB>
 hipError_t launch_verify_m(uint64_t blocks, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
                            uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
-                           const uint32_t* d_combB, void* d_ws, uint64_t* d_out_words, hipStream_t s, int per_lane) {
+                           const uint32_t* d_combB, void* d_ws, uint64_t* d_out_words, hipStream_t s, int per_lane,
+                           XTab xt) {
   const int occ = verify_occupancy();
 #define NT_V_LAUNCH(O, P)                                                                                  \
   hipLaunchKernelGGL((k_ed25519_verify<MODE, O, WB, P>), dim3((uint32_t)blocks), dim3(kBlock), 0, s,          \
                      (const uint32_t*)d_pk, (const uint32_t*)d_sig, d_msg, msg_bytes, d_off, d_len, n, d_combB, \
-                     (uint4*)d_ws, (unsigned long long*)d_out_words)
+                     (uint4*)d_ws, (unsigned long long*)d_out_words, (uint4*)xt.tab, xt.mask)
   if (per_lane == 1 && kVPer != 1) {
     if (occ != 2) return hipErrorInvalidValue;  // verify_per_lane_for() never asks for it
     NT_V_LAUNCH(2, 1);

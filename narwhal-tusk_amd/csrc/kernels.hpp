@@ -18,10 +18,26 @@ namespace nt {
 hipError_t launch_sha512_trunc32(const uint8_t* d_data, uint64_t data_bytes, const uint64_t* d_off,
                                  const uint64_t* d_len, uint64_t n, uint8_t* d_out32, hipStream_t s,
                                  uint64_t max_len = ~0ull, uint32_t* d_bad = nullptr);
+// The x cache of a verify launch (kernels_common.hpp DevXCache): mask + 1 slots of 32 bytes
+// (a power of two), tab == nullptr = no table.
+struct XTab {
+  void* tab = nullptr;
+  uint32_t mask = 0;
+};
+// slot count of an x cache asked for as `want` slots: rounded down to a power of two, at most
+// `cap` (a power of two); 0 = none
+constexpr uint32_t kXCacheSlotsDefault = 1u << 21;  // 64 MB
+constexpr uint32_t kXCacheSlotsMax = 1u << 28;      // 8 GB
+inline uint32_t xcache_slots_pow2(unsigned long long want, uint32_t cap) {
+  if (want == 0) return 0;
+  uint32_t s = 1;
+  while (s < cap && 2ull * s <= want) s <<= 1;
+  return s;
+}
 hipError_t launch_verify(int mode, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
                          uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
                          const uint32_t* d_combB, int bbits, void* d_ws, uint32_t ws_slots, uint64_t* d_out_words,
-                         hipStream_t s, int per_lane = 0);
+                         hipStream_t s, int per_lane = 0, XTab xt = XTab());
 hipError_t launch_group_and(const uint64_t* d_first, const uint32_t* d_cnt, uint64_t G,
                             const uint64_t* d_sig_words, uint64_t* d_group_words, hipStream_t s);
 // off[first[g] + q] = 32 g, len = 32 for q < cnt[g] (groups' 32-byte messages)

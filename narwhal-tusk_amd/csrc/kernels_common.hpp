@@ -201,6 +201,30 @@ struct WsATab {
 #endif
 };
 
+// The x cache of the verify kernel (ed25519_ops.hpp XCache): `msk + 1` slots of
+// two uint4 in global memory, one table per device entry, read and written by
+// launches on any stream with no ordering between them -- a slot is only ever a
+// candidate (ge_frombytes_x_check).  Callers keep every index <= msk, the
+// allocated size - 1 (xcache_cand); tab == nullptr: no table (every wave takes
+// the slow path, nothing is stored).
+struct DevXCache {
+  static constexpr bool kEnabled = true;
+  uint4* tab;
+  uint32_t msk;
+  NT_D NT_INLINE bool active() const { return tab != nullptr; }
+  NT_D NT_INLINE uint32_t mask() const { return msk; }
+  NT_D NT_INLINE void load(uint32_t i, uint32_t xw[8]) const {
+    const uint4* e = tab + 2 * (size_t)(i & msk);
+    const uint4 a = e[0], b = e[1];
+    xw[0] = a.x; xw[1] = a.y; xw[2] = a.z; xw[3] = a.w; xw[4] = b.x; xw[5] = b.y; xw[6] = b.z; xw[7] = b.w;
+  }
+  NT_D NT_INLINE void store(uint32_t i, const uint32_t xw[8]) const {
+    uint4* e = tab + 2 * (size_t)(i & msk);
+    e[0] = make_uint4(xw[0], xw[1], xw[2], xw[3]);
+    e[1] = make_uint4(xw[4], xw[5], xw[6], xw[7]);
+  }
+};
+
 // ---- key-cache verification: up to 64 signatures per lane, one inversion ----
 #ifndef NT_KS_PER_LANE
 #define NT_KS_PER_LANE 64
@@ -303,7 +327,8 @@ struct KsVerdict {
 template <int MODE, int WB>
 hipError_t launch_verify_m(uint64_t blocks, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
                            uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
-                           const uint32_t* d_combB, void* d_ws, uint64_t* d_out_words, hipStream_t s, int per_lane);
+                           const uint32_t* d_combB, void* d_ws, uint64_t* d_out_words, hipStream_t s, int per_lane,
+                           XTab xt);
 template <int MODE, int WA, int WB>
 hipError_t launch_keyset_m(const KsPlan& plan, const uint32_t* d_key_idx, const uint8_t* d_sig, const uint8_t* d_msg,
                            uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n, const uint32_t* d_meta,

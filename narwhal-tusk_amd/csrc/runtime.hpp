@@ -109,14 +109,17 @@ int comb_b_for(Device& dv);
 // the comb of B (24 -> 20 bits) and the committee key combs (20 -> 18 -> 16) --
 // are reserved against `limit` (NT_HBM_BUDGET / nt_set_hbm_budget; 0 = no cap,
 // only the device's free memory decides).  Workspaces, stashes and staging are
-// per-call and not budgeted (nt_memory_info reports them).
+// per-call and not budgeted (nt_memory_info reports them).  The x cache (one fixed-size table
+// per entry, no width to degrade) counts against the same limit in `aux`, beside the combs'
+// `held` that nt_memory_info reports.
 struct Budget {
   std::mutex mu;
   uint64_t limit = 0;
   uint64_t held = 0;
+  uint64_t aux = 0;
   bool reserve(uint64_t b) {
     std::lock_guard<std::mutex> lk(mu);
-    if (limit && held + b > limit) return false;
+    if (limit && held + aux + b > limit) return false;
     held += b;
     return true;
   }
@@ -124,9 +127,19 @@ struct Budget {
     std::lock_guard<std::mutex> lk(mu);
     held -= std::min(held, b);
   }
+  bool reserve_aux(uint64_t b) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (limit && held + aux + b > limit) return false;
+    aux += b;
+    return true;
+  }
+  void release_aux(uint64_t b) {
+    std::lock_guard<std::mutex> lk(mu);
+    aux -= std::min(aux, b);
+  }
   bool fits(uint64_t b) {
     std::lock_guard<std::mutex> lk(mu);
-    return !limit || held + b <= limit;
+    return !limit || held + aux + b <= limit;
   }
 };
 
@@ -172,6 +185,15 @@ struct Device {
   int bbits = 0;                // its digit width (nt::kBCombBits or nt::kBCombFallback)
   std::atomic<int> comb_ready{0};  // this slot's d_combB / bbits are set (comb_b_for's lock-free fast path)
   void* d_ws = nullptr;         // verify workspace: ensure_ws() on the first verify
+  // The x cache (ed25519_ops.hpp XCache): uint4 xtab[xslots][2], one table per device entry,
+  // shared by its execution slots and both workspaces; xcache_for() (context.cpp) allocates it
+  // zero-filled with the first verify and hands every slot the entry's pointer.  Null = none
+  // (NT_XCACHE_SLOTS=0, or it did not fit the budget / the device).
+  void* d_xtab = nullptr;
+  uint32_t xslots = 0;          // a power of two
+  uint64_t xtab_reserved = 0;   // (entry) its bytes in the budget
+  bool xtab_tried = false;      // (entry) under tables_mu
+  std::atomic<int> xtab_ready{0};  // this slot's d_xtab / xslots are set
   uint32_t ws_slots = 0;
   uint32_t sign_blocks = 0;
   uint32_t cus = 0;
@@ -205,6 +227,7 @@ struct Device {
 
   ~Device() {
     if (comb_reserved && budget) budget->release(comb_reserved);
+    if (xtab_reserved && budget) budget->release_aux(xtab_reserved);
     if (ordinal < 0) return;
     (void)hipSetDevice(ordinal);
     if (stream) (void)hipStreamSynchronize(stream);
@@ -220,6 +243,7 @@ struct Device {
     for (auto& e : cev)
       if (e) (void)hipEventDestroy(e);
     if (stream2 && stream2 != stream) (void)hipStreamSynchronize(stream2);
+    if (entry == this && d_xtab) (void)hipFree(d_xtab);
     if (ws2.p) (void)hipFree(ws2.p);
     if (stash2.p) (void)hipFree(stash2.p);
     if (sort2.p) (void)hipFree(sort2.p);
@@ -319,6 +343,21 @@ struct Device {
     return NT_OK;
   }
 
+  // The x cache as a launch sees it.  NT_XCACHE_SLOTS is read again at every launch: a value
+  // below the allocated size confines the launch to the table's first slots (0: no cache for
+  // this launch), a larger one changes nothing.
+  nt::XTab xtab() const {
+    nt::XTab xt;
+    if (!d_xtab) return xt;
+    uint32_t slots = xslots;
+    if (const char* e = std::getenv("NT_XCACHE_SLOTS")) slots = nt::xcache_slots_pow2(std::strtoull(e, nullptr, 10), xslots);
+    if (slots) {
+      xt.tab = d_xtab;
+      xt.mask = slots - 1;
+    }
+    return xt;
+  }
+
   // compute stream of chunk c
   hipStream_t cstr(int c) const { return (c & 1) ? stream2 : stream; }
 
@@ -334,7 +373,7 @@ struct Device {
     if (rc != NT_OK) return rc;
     if (hipStreamWaitEvent(stream2, ws2_done, 0) != hipSuccess ||
         nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, ws2.p,
-                          (uint32_t)std::max<uint64_t>(blocks, 1), out, stream2, per_lane) != hipSuccess ||
+                          (uint32_t)std::max<uint64_t>(blocks, 1), out, stream2, per_lane, xtab()) != hipSuccess ||
         hipEventRecord(ws2_done, stream2) != hipSuccess)
       return NT_EHIP;
     return NT_OK;
@@ -391,7 +430,8 @@ struct Device {
     if (grow_ws2(ws_slots) != NT_OK) return hipErrorOutOfMemory;
     hipError_t e = hipStreamWaitEvent(s, ws2_done, 0);
     if (e != hipSuccess) return e;
-    e = nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, ws2.p, ws_slots, out, s);
+    e = nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, ws2.p, ws_slots, out, s, 0,
+                          xtab());
     if (e != hipSuccess) return e;
     return hipEventRecord(ws2_done, s);
   }
@@ -403,7 +443,7 @@ struct Device {
     hipError_t e = hipStreamWaitEvent(s, ws_done, 0);
     if (e != hipSuccess) return e;
     e = nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, d_ws, ws_slots, out, s,
-                          per_lane);
+                          per_lane, xtab());
     if (e != hipSuccess) return e;
     return hipEventRecord(ws_done, s);
   }
