@@ -252,6 +252,33 @@ void nt_committee_free(nt_committee *cm);
  * nt_host_alloc memory are DMA'd straight from it. */
 int nt_certificates_ingest(nt_ctx *ctx, const nt_committee *cm, const uint8_t *data, const uint64_t *off,
                            const uint64_t *len, uint64_t n, uint64_t gc_round, uint8_t *out_code);
+/* The whole drain: all four kinds of PrimaryMessage that Core::run sanitises
+ * (core.rs:349-376) decided in the same pass -- same chunking, streams,
+ * sharding and pinned-input rule as nt_certificates_ingest, and a certificate
+ * gets exactly the code that call gives it.  Slot i of the chunk's one
+ * NT_MODE_MIXED launch is message i's own strict signature, SHA-512 input i
+ * its preimage:
+ *   Header   (core.rs:306-318, messages.rs:48-67)  round < gc_round: TooOld;
+ *            then the id, the author's stake, the workers, the signature over
+ *            the claimed id.  No genesis shortcut: that is a certificate rule.
+ *   Vote     (core.rs:320-336, messages.rs:131-142)  round < cur_round: TooOld;
+ *            (id, origin's raw key, round) != the current header's:
+ *            UnexpectedVote; the author's stake 0: UnknownAuthority; then the
+ *            signature over the digest of id || round || origin.
+ *   Request  from a committee key: UnexpectedMessage (core.rs:374).
+ * cur_id32 / cur_round / cur_author32: the header currently being voted on
+ * (Core::current_header); a NULL id or author is 32 zero bytes
+ * (Header::default()).  cur_author32 is a raw key, not necessarily a
+ * committee key.  NT_DAG_HOST as above: malformed or truncated bytes, a tag
+ * above 3, a key string (a vote's origin and a request's requestor included)
+ * that is not a committee key's canonical text, entries out of canonical
+ * order.  SerializationError (9) is the host decoder's to give, never this
+ * call's. */
+#define NT_DAG_UNEXPECTED_VOTE 8
+#define NT_DAG_UNEXPECTED_MESSAGE 10
+int nt_primary_messages_ingest(nt_ctx *ctx, const nt_committee *cm, const uint8_t *data, const uint64_t *off,
+                               const uint64_t *len, uint64_t n, uint64_t gc_round, const uint8_t *cur_id32,
+                               uint64_t cur_round, const uint8_t *cur_author32, uint8_t *out_code);
 
 /* ---- small-call path (SURVEY.md H3, §8(b) "CPU-fallback threshold") ------
  * The reference calls verify once per header / vote, verify_batch once per

@@ -1,6 +1,7 @@
-// ingest_gpu.cpp -- C ABI of the certificate ingestion from wire bytes
-// (include/ntcrypto.h: nt_committee_*, nt_certificates_ingest; kernels in
-// k_ingest.hip).
+// ingest_gpu.cpp -- C ABI of the message ingestion from wire bytes
+// (include/ntcrypto.h: nt_committee_*, nt_certificates_ingest,
+// nt_primary_messages_ingest; kernels in k_ingest.hip).  The two entry points
+// share everything below; they differ in the kinds the kernels decide.
 //
 // Per device shard the messages are cut into chunks that alternate between
 // the slot's two compute streams.  A chunk is two halves:
@@ -22,6 +23,7 @@
 
 #include "../../include/ntcrypto.h"
 #include "kernels.hpp"
+#include "msg_plan.hpp"
 #include "runtime.hpp"
 
 using namespace ntrt;
@@ -194,9 +196,16 @@ void nt_committee_free(nt_committee* cm) { delete cm; }
 
 namespace {
 
+// what one call decides: the kinds, the GC round and the header being voted on
+struct IngestRules {
+  uint32_t kinds = nt::kMsgKindsCert;
+  uint64_t gc_round = 0;
+  nt::MsgCurrent cur{};
+};
+
 // front half of chunk ch on stream s (see the file comment)
 int ingest_front(Device& dv, IngestState& S, Side& sd, Chunk& ch, const nt_committee::PerDev& pd,
-                 const uint8_t* data, const uint64_t* off, const uint64_t* len, hipStream_t s) {
+                 const uint8_t* data, const uint64_t* off, const uint64_t* len, uint32_t kinds, hipStream_t s) {
   const uint64_t m = ch.b - ch.a;
   uint64_t* ho = S.hoff.as<uint64_t>() + ch.a;
   uint64_t* hl = S.hlen.as<uint64_t>() + ch.a;
@@ -237,6 +246,7 @@ int ingest_front(Device& dv, IngestState& S, Side& sd, Chunk& ch, const nt_commi
   b.moff = sd.moff.as<uint64_t>();
   b.mlen = sd.mlen.as<uint64_t>();
   b.n = m;
+  b.kinds = kinds;
   b.round = sd.round.as<uint64_t>();
   uint32_t* u = sd.u32s.as<uint32_t>();
   b.author = u;
@@ -265,7 +275,7 @@ int ingest_front(Device& dv, IngestState& S, Side& sd, Chunk& ch, const nt_commi
 }
 
 int ingest_back(Device& dv, IngestState& S, Side& sd, int parity, Chunk& ch, const nt_committee& cm,
-                const nt_committee::PerDev& pd, uint64_t gc_round, hipStream_t s) {
+                const nt_committee::PerDev& pd, const IngestRules& rules, hipStream_t s) {
   const uint64_t m = ch.b - ch.a;
   NT_TRY(hipEventSynchronize(sd.ev));
   const uint64_t V = sd.tot.as<uint64_t>()[0], P = sd.tot.as<uint64_t>()[1];
@@ -299,13 +309,13 @@ int ingest_back(Device& dv, IngestState& S, Side& sd, int parity, Chunk& ch, con
                                     st, so, sd.words.as<uint64_t>(), dv.cus, s, b.gfirst, b.gcnt, m,
                                     (uint64_t*)b.grp_words);  // the vote groups' AND in the kernel's epilogue
   }));
-  NT_TRY(nt::launch_cert_verdict(pd.c, b, gc_round, s));
+  NT_TRY(nt::launch_cert_verdict(pd.c, b, rules.gc_round, rules.cur, s));
   NT_TRY(hipMemcpyAsync(S.hcode.as<uint8_t>() + ch.a, b.code, m, hipMemcpyDeviceToHost, s));
   return NT_OK;
 }
 
 int ingest_shard(Device& dv, const nt_committee& cm, const uint8_t* data, const uint64_t* off, const uint64_t* len,
-                 uint64_t lo, uint64_t hi, uint64_t gc_round, uint8_t* out) {
+                 uint64_t lo, uint64_t hi, const IngestRules& rules, uint8_t* out) {
   const uint64_t n = hi - lo;
   if (!n) return NT_OK;
   NT_CHK0(comb_b_for(dv));
@@ -335,8 +345,8 @@ int ingest_shard(Device& dv, const nt_committee& cm, const uint8_t* data, const 
   const uint64_t* o = off + lo;
   const uint64_t* l = len + lo;
   for (size_t k = 0; k <= ch.size(); ++k) {
-    if (k < ch.size()) NT_CHK0(ingest_front(dv, S, S.side[k & 1], ch[k], pd, d, o, l, dv.cstr((int)k)));
-    if (k >= 1) NT_CHK0(ingest_back(dv, S, S.side[(k - 1) & 1], (int)((k - 1) & 1), ch[k - 1], cm, pd, gc_round,
+    if (k < ch.size()) NT_CHK0(ingest_front(dv, S, S.side[k & 1], ch[k], pd, d, o, l, rules.kinds, dv.cstr((int)k)));
+    if (k >= 1) NT_CHK0(ingest_back(dv, S, S.side[(k - 1) & 1], (int)((k - 1) & 1), ch[k - 1], cm, pd, rules,
                                     dv.cstr((int)(k - 1))));
   }
   NT_TRY(hipStreamSynchronize(dv.stream));
@@ -345,18 +355,38 @@ int ingest_shard(Device& dv, const nt_committee& cm, const uint8_t* data, const 
   return NT_OK;
 }
 
+int ingest_call(nt_ctx* ctx, const nt_committee* cm, const uint8_t* data, const uint64_t* off, const uint64_t* len,
+                uint64_t n, const IngestRules& rules, uint8_t* out_code) {
+  if (!ctx || !cm || cm->ctx != ctx || (n && (!data || !off || !len || !out_code))) return NT_EINVAL;
+  if (n == 0) return NT_OK;
+  ctx->calls_gpu++;
+  return run_sharded(ctx, n, 1, [&](Device& dv, uint64_t lo, uint64_t hi) {
+    return ingest_shard(dv, *cm, data, off, len, lo, hi, rules, out_code);
+  });
+}
+
 }  // namespace
 
 extern "C" {
 
 int nt_certificates_ingest(nt_ctx* ctx, const nt_committee* cm, const uint8_t* data, const uint64_t* off,
                            const uint64_t* len, uint64_t n, uint64_t gc_round, uint8_t* out_code) {
-  if (!ctx || !cm || cm->ctx != ctx || (n && (!data || !off || !len || !out_code))) return NT_EINVAL;
-  if (n == 0) return NT_OK;
-  ctx->calls_gpu++;
-  return run_sharded(ctx, n, 1, [&](Device& dv, uint64_t lo, uint64_t hi) {
-    return ingest_shard(dv, *cm, data, off, len, lo, hi, gc_round, out_code);
-  });
+  IngestRules rules;
+  rules.gc_round = gc_round;
+  return ingest_call(ctx, cm, data, off, len, n, rules, out_code);
+}
+
+int nt_primary_messages_ingest(nt_ctx* ctx, const nt_committee* cm, const uint8_t* data, const uint64_t* off,
+                               const uint64_t* len, uint64_t n, uint64_t gc_round, const uint8_t* cur_id32,
+                               uint64_t cur_round, const uint8_t* cur_author32, uint8_t* out_code) {
+  IngestRules rules;
+  rules.kinds = nt::kMsgKindsAll;
+  rules.gc_round = gc_round;
+  rules.cur.round = cur_round;  // a null id / author: 32 zero bytes (Header::default())
+  if (cur_id32) std::memcpy(&rules.cur.w[0], cur_id32, 32);
+  std::memcpy(&rules.cur.w[8], &cur_round, 8);
+  if (cur_author32) std::memcpy(&rules.cur.w[10], cur_author32, 32);
+  return ingest_call(ctx, cm, data, off, len, n, rules, out_code);
 }
 
 }  // extern "C"

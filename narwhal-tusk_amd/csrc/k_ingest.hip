@@ -1,42 +1,46 @@
-// k_ingest.hip -- the primary's certificate ingestion on the device (SURVEY
-// §8(f).2): bincode PrimaryMessage::Certificate bytes, copied to HBM as they
-// arrived from the network (primary/src/primary.rs:225-244), are parsed,
-// checked in Certificate::verify's order (primary/src/messages.rs:189-215,
-// with Core::sanitize_certificate's round filter, core.rs:339-346) and turned
-// into the key-cache launch buffers without a host decode.
+// k_ingest.hip -- the primary's message ingestion on the device (SURVEY
+// §8(f).2): bincode PrimaryMessage bytes, copied to HBM as they arrived from
+// the network (primary/src/primary.rs:225-244), are parsed, checked in the
+// order of Core::sanitize_header / _vote / _certificate (core.rs:306-346) and
+// Header / Vote / Certificate::verify (primary/src/messages.rs:48-67, 131-142,
+// 189-215) and turned into the key-cache launch buffers without a host decode.
+// CertBufs::kinds says which kinds a call decides: certificates only
+// (nt_certificates_ingest) or all four (nt_primary_messages_ingest).
 //
-//   k_cert_parse    one wave per message: layout, base64 key strings -> committee
-//                   indices, canonical (strictly increasing) payload / parents,
-//                   payload workers; anything irregular -> "host" (the host
-//                   decoder decides those messages)
+//   k_cert_parse    one wave per message: layout (msg_plan.hpp), base64 key
+//                   strings -> committee indices, canonical (strictly increasing)
+//                   payload / parents, payload workers; anything irregular ->
+//                   "host" (the host decoder decides those messages)
 //   k_cert_scan     exclusive scans of the vote counts and preimage lengths
-//   k_cert_scatter  one wave per message: the header signature and every vote
-//                   (key index, signature, message) into the dense arrays of ONE
-//                   NT_MODE_MIXED key-cache launch, the header digest preimage
-//                   (author || round || payload || parents) and the certificate
-//                   digest preimage, the votes' first reuse / unknown error and
-//                   the stake they carry
+//   k_cert_scatter  one wave per message: the message's own signature and every
+//                   certificate vote (key index, signature, message) into the
+//                   dense arrays of ONE NT_MODE_MIXED key-cache launch, the header
+//                   digest preimage (author || round || payload || parents), the
+//                   certificate or vote digest preimage, the votes' first reuse /
+//                   unknown error and the stake they carry
 //   k_cert_verdict  one thread per message: the DagError of the first failing
 //                   check, in the reference order
 // Message bytes are read with aligned dword loads joined by v_alignbyte (the
 // wire buffer keeps 64 bytes of slack on both sides), so messages may start
 // at any byte.
 #include "kernels_common.hpp"
+#include "msg_plan.hpp"
 
 namespace nt {
 
 namespace {
 
 constexpr uint32_t kMiss = 0xffffffffu;
-constexpr uint32_t kCertHost = 1u, kCertWorkersBad = 2u;
-constexpr uint32_t kMaxVotes = 1024;        // larger certificates go to the host decoder
-constexpr uint64_t kMaxEntries = 1u << 20;  // payload / parents entries (ditto)
+constexpr uint32_t kCertHost = 1u, kCertWorkersBad = 2u;  // CertBufs::flags; the message kind in bits 4-5
+constexpr int kFlagKindShift = 4;
+constexpr uint32_t kMaxVotes = kMsgMaxVotes;
 constexpr int kWavesPerBlock = kBlock / 64;
 
 // primary::DagError (host/narwhal.hpp; the reference's error.rs variants)
 enum : uint32_t {
   kDagOk = 0, kDagInvalidSignature = 1, kDagInvalidHeaderId = 2, kDagMalformedHeader = 3,
   kDagUnknownAuthority = 4, kDagAuthorityReuse = 5, kDagRequiresQuorum = 6, kDagTooOld = 7,
+  kDagUnexpectedVote = 8, kDagUnexpectedMessage = 10,
 };
 
 NT_D NT_INLINE uint32_t ldu32(const uint8_t* p) {
@@ -45,6 +49,12 @@ NT_D NT_INLINE uint32_t ldu32(const uint8_t* p) {
   return __builtin_amdgcn_alignbyte(q[1], q[0], (uint32_t)(a & 3));
 }
 NT_D NT_INLINE uint64_t ldu64(const uint8_t* p) { return ldu32(p) | ((uint64_t)ldu32(p + 4) << 32); }
+// msg_plan.hpp's loader over the wire bytes of one message
+struct WireLd {
+  const uint8_t* p;
+  NT_D NT_INLINE uint32_t u32(uint64_t o) const { return ldu32(p + o); }
+  NT_D NT_INLINE uint64_t u64(uint64_t o) const { return ldu64(p + o); }
+};
 template <int N>
 NT_D NT_INLINE void ldwords(const uint8_t* p, uint32_t w[N]) {
   const uintptr_t a = (uintptr_t)p;
@@ -105,10 +115,8 @@ NT_D NT_INLINE bool wave_any(bool x) { return __ballot(x) != 0; }
 
 }  // namespace
 
-// Wire layout of PrimaryMessage::Certificate (bincode 1.x, fixint, little
-// endian; host/wire.cpp): u32 tag = 2 | u64 44 | author base64 (44) | u64
-// round | u64 np | np x (digest 32, worker u32) | u64 nq | nq x digest 32 |
-// id 32 | signature 64 | u64 nv | nv x (u64 44 | key base64 (44) | signature 64)
+// The layouts are msg_plan.hpp's.  A header is a certificate without votes; a
+// vote and a request carry no map / set, so only their key strings are looked up.
 __global__ __launch_bounds__(kBlock) void k_cert_parse(CertCommittee c, CertBufs b) {
   aux_priority();
   const uint64_t i = (uint64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
@@ -116,70 +124,45 @@ __global__ __launch_bounds__(kBlock) void k_cert_parse(CertCommittee c, CertBufs
   if (i >= b.n) return;  // whole waves
   const uint8_t* p = b.wire + b.moff[i];
   const uint64_t L = b.mlen[i];
-  bool host = false, wbad = false;
-  uint32_t author = 0;
-  uint64_t round = 0, np = 0, nq = 0, nv = 0, off_par = 0, off_votes = 0;
   // every value below is the same in all lanes (wave-uniform control flow)
-  if (L < 72 || ldu32(p) != 2u || ldu64(p + 4) != 44u) host = true;
+  const WireLd ld{p};
+  const MsgPlan m = msg_walk(ld, L, b.kinds);
+  bool host = m.kind == kMsgHost, wbad = false;
+  uint32_t author = 0;
   if (!host) {
-    author = key_lookup(c, p + 12);
-    round = ldu64(p + 56);
-    np = ldu64(p + 64);
-    uint64_t pos = 72;
-    if (author == kMiss || np > (L - pos) / 36 || np > kMaxEntries) {
-      host = true;
-    } else {
-      pos += 36 * np;
-      if (L - pos < 8) {
-        host = true;
-      } else {
-        nq = ldu64(p + pos);
-        pos += 8;
-        if (nq > (L - pos) / 32 || nq > kMaxEntries) {
-          host = true;
-        } else {
-          off_par = pos;
-          pos += 32 * nq;
-          if (L - pos < 104) {
-            host = true;
-          } else {
-            pos += 96;
-            nv = ldu64(p + pos);
-            pos += 8;
-            if (nv > (L - pos) / 116 || nv > kMaxVotes) host = true;
-            off_votes = pos;
-          }
-        }
-      }
-    }
+    author = key_lookup(c, p + m.key0);
+    // a vote: key0 is the origin (looked up again by k_cert_scatter), key1 the author
+    if (author != kMiss && m.kind == kMsgVote) author = key_lookup(c, p + m.key1);
+    host = author == kMiss;
   }
-  if (!host) {
+  if (!host) {  // a vote or a request has np = nq = nv = 0
     bool bad = false;
-    for (uint64_t v = lane; v < nv; v += 64) {
-      const uint8_t* q = p + off_votes + 116 * v;
-      if (ldu64(q) != 44u || key_lookup(c, q + 8) == kMiss) bad = true;
+    for (uint64_t v = lane; v < m.nv; v += 64) {
+      const uint64_t q = msg_cert_vote_key(ld, m, v);
+      if (q == 0 || key_lookup(c, p + q) == kMiss) bad = true;
     }
     const uint32_t w0 = c.wfirst[author], wn = c.wfirst[author + 1] - w0;
-    for (uint64_t k = lane; k < np; k += 64) {
+    for (uint64_t k = lane; k < m.np; k += 64) {
       const uint8_t* e = p + 72 + 36 * k;
       if (k && cmp32(e - 36, e) >= 0) bad = true;  // BTreeMap order, no repeats
       if (!in_sorted(c.wids + w0, wn, ldu32(e + 32))) wbad = true;
     }
-    for (uint64_t k = lane + 1; k < nq; k += 64) {
-      const uint8_t* e = p + off_par + 32 * k;
+    for (uint64_t k = lane + 1; k < m.nq; k += 64) {
+      const uint8_t* e = p + m.off_par + 32 * k;
       if (cmp32(e - 32, e) >= 0) bad = true;  // BTreeSet order, no repeats
     }
     host = wave_any(bad);
     wbad = wave_any(wbad);
   }
   if (lane == 0) {
-    b.round[i] = round;
+    const bool hdr = !host && (m.kind == kMsgHeader || m.kind == kMsgCert);
+    b.round[i] = m.round;
     b.author[i] = author;
-    b.np[i] = host ? 0u : (uint32_t)np;
-    b.nq[i] = host ? 0u : (uint32_t)nq;
-    b.nv[i] = host ? 0u : (uint32_t)nv;
-    b.flags[i] = (host ? kCertHost : 0u) | (wbad ? kCertWorkersBad : 0u);
-    b.plen[i] = host ? 0u : (uint32_t)(40 + 36 * np + 32 * nq);
+    b.np[i] = host ? 0u : (uint32_t)m.np;
+    b.nq[i] = host ? 0u : (uint32_t)m.nq;
+    b.nv[i] = host ? 0u : (uint32_t)m.nv;
+    b.flags[i] = host ? kCertHost : (wbad ? kCertWorkersBad : 0u) | (m.kind << kFlagKindShift);
+    b.plen[i] = hdr ? (uint32_t)(40 + 36 * m.np + 32 * m.nq) : 0u;
   }
 }
 
@@ -223,7 +206,10 @@ __global__ __launch_bounds__(1024) void k_cert_scan(CertBufs b) {
 // (strict: key | NT_KEY_STRICT_BIT, message = the claimed id), n + vbase[i] +
 // v = vote v (cofactorless, message = the certificate digest computed by the
 // SHA-512 launch); SHA-512 inputs i (header preimage) and n + i (certificate
-// preimage id || round || origin, messages.rs:226-234).
+// preimage id || round || origin, messages.rs:226-234).  A header uses the same
+// entries with no votes and input n + i empty; a vote's entry i is its own
+// signature over digest i of id || round || origin, written where a certificate's
+// preimage goes.
 __global__ __launch_bounds__(kBlock) void k_cert_scatter(CertCommittee c, CertBufs b) {
   aux_priority();
   __shared__ uint32_t vkey[kWavesPerBlock][kMaxVotes];
@@ -237,7 +223,9 @@ __global__ __launch_bounds__(kBlock) void k_cert_scatter(CertCommittee c, CertBu
   uint32_t* sw = (uint32_t*)b.sigs;
   uint32_t* mw = (uint32_t*)b.mbase;
   const uint64_t vb = b.vbase[i];
-  if (fl & kCertHost) {  // the host decoder decides this message: inert entries
+  const uint32_t kind = fl >> kFlagKindShift;
+  // the host decoder decides this message, or it is a request (nothing to verify): inert entries
+  if ((fl & kCertHost) || kind == kMsgRequest) {
     if (lane < 16) sw[16 * i + lane] = 0;
     if (lane < 8) mw[hid_off / 4 + lane] = 0;
     if (lane < 18) mw[cpre_off / 4 + lane] = 0;
@@ -256,9 +244,33 @@ __global__ __launch_bounds__(kBlock) void k_cert_scatter(CertCommittee c, CertBu
     }
     return;
   }
+  const uint32_t a = b.author[i];
+  if (kind == kMsgVote) {
+    // signature i is the author's, strict, over the digest the SHA-512 launch writes for
+    // input i = id || round_le || origin (messages.rs:145-153; id and round are adjacent
+    // in the wire); k_cert_verdict compares the same 72 bytes with the current header
+    const uint32_t* org = c.raw + 8 * (size_t)key_lookup(c, p + 52);  // found (k_cert_parse)
+    if (lane < 16) sw[16 * i + lane] = ldu32(p + 148 + 4 * lane);
+    if (lane < 8) mw[hid_off / 4 + lane] = 0;
+    if (lane < 18) mw[cpre_off / 4 + lane] = lane < 10 ? ldu32(p + 4 + 4 * lane) : org[lane - 10];
+    if (lane == 0) {
+      b.keys[i] = a | kKeyWantStrict;
+      b.smoff[i] = 32 * n + 32 * i;
+      b.smlen[i] = 32;
+      b.soff[i] = cpre_off;
+      b.slen[i] = 72;
+      b.soff[n + i] = cpre_off;
+      b.slen[n + i] = 0;
+      b.gfirst[i] = n + vb;
+      b.gcnt[i] = 0;
+      b.verr[i] = 0;
+      b.weight[i] = 0;
+    }
+    return;
+  }
+  // a header is a certificate without votes: an empty group, no certificate digest
   const uint64_t np = b.np[i], nq = b.nq[i], nv = b.nv[i];
   const uint64_t off_par = 80 + 36 * np, off_id = off_par + 32 * nq, off_sig = off_id + 32, off_votes = off_id + 104;
-  const uint32_t a = b.author[i];
   const uint64_t round = b.round[i];
   const uint32_t* raw = c.raw + 8 * (size_t)a;
   if (lane < 16) sw[16 * i + lane] = ldu32(p + off_sig + 4 * lane);
@@ -324,7 +336,7 @@ __global__ __launch_bounds__(kBlock) void k_cert_scatter(CertCommittee c, CertBu
     b.soff[i] = b.pre_off + b.pbase[i];
     b.slen[i] = plen;
     b.soff[n + i] = cpre_off;
-    b.slen[n + i] = 72;
+    b.slen[n + i] = kind == kMsgCert ? 72 : 0;
     b.gfirst[i] = n + vb;
     b.gcnt[i] = (uint32_t)nv;
   }
@@ -335,15 +347,32 @@ NT_D NT_INLINE bool word_bit(const uint64_t* w, uint64_t i) { return (w[i >> 6] 
 // DagError of message i, first failing check in the reference order: the round
 // filter (core.rs:339-342), genesis (messages.rs:190-193), Header::verify's id,
 // author, workers and signature (:48-67), the quorum loop (:198-211), the votes'
-// verify_batch (:213); 0xff = decided by the host decoder
-__global__ __launch_bounds__(kBlock) void k_cert_verdict(CertCommittee c, CertBufs b, uint64_t gc_round) {
+// verify_batch (:213); 0xff = decided by the host decoder.  A header
+// (core.rs:306-318) takes the same path up to its signature, without the
+// genesis shortcut, which is a certificate rule.  A vote (core.rs:320-336,
+// messages.rs:131-142): its round against the current header's, then (id,
+// round, origin) against the current header, the author's stake, the signature.
+// A request is UnexpectedMessage (core.rs:374).
+__global__ __launch_bounds__(kBlock) void k_cert_verdict(CertCommittee c, CertBufs b, uint64_t gc_round,
+                                                         MsgCurrent cur) {
   aux_priority();
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= b.n) return;
-  const uint32_t fl = b.flags[i];
+  const uint32_t fl = b.flags[i], kind = fl >> kFlagKindShift;
   uint32_t code = kDagOk;
   if (fl & kCertHost) {
     code = 0xffu;
+  } else if (kind == kMsgRequest) {
+    code = kDagUnexpectedMessage;
+  } else if (kind == kMsgVote) {
+    const uint32_t* v = (const uint32_t*)(b.mbase + 96 * b.n + 72 * i);  // id || round_le || origin (k_cert_scatter)
+    uint32_t same = 1;
+#pragma unroll
+    for (int j = 0; j < 18; ++j) same &= v[j] == cur.w[j];
+    if (b.round[i] < cur.round) code = kDagTooOld;
+    else if (!same) code = kDagUnexpectedVote;
+    else if (c.stake[b.author[i]] == 0) code = kDagUnknownAuthority;
+    else if (!word_bit(b.sig_words, i)) code = kDagInvalidSignature;
   } else if (b.round[i] < gc_round) {
     code = kDagTooOld;
   } else {
@@ -355,11 +384,12 @@ __global__ __launch_bounds__(kBlock) void k_cert_verdict(CertCommittee c, CertBu
       zero &= hid[j] == 0u;
       same &= hid[j] == dig[j];
     }
-    if (zero && b.round[i] == 0) code = kDagOk;  // a committee member's genesis certificate
+    if (kind == kMsgCert && zero && b.round[i] == 0) code = kDagOk;  // a committee member's genesis certificate
     else if (!same) code = kDagInvalidHeaderId;
     else if (c.stake[b.author[i]] == 0) code = kDagUnknownAuthority;
     else if (fl & kCertWorkersBad) code = kDagMalformedHeader;
     else if (!word_bit(b.sig_words, i)) code = kDagInvalidSignature;
+    else if (kind == kMsgHeader) code = kDagOk;  // Header::verify ends here; the rest is Certificate::verify
     else if (b.verr[i]) code = b.verr[i];
     else if (b.weight[i] < c.quorum) code = kDagRequiresQuorum;
     else if (!word_bit(b.grp_words, i)) code = kDagInvalidSignature;
@@ -384,10 +414,11 @@ hipError_t launch_cert_scatter(const CertCommittee& c, const CertBufs& b, hipStr
   hipLaunchKernelGGL(k_cert_scatter, dim3((uint32_t)blocks), dim3(kBlock), 0, s, c, b);
   return hipGetLastError();
 }
-hipError_t launch_cert_verdict(const CertCommittee& c, const CertBufs& b, uint64_t gc_round, hipStream_t s) {
+hipError_t launch_cert_verdict(const CertCommittee& c, const CertBufs& b, uint64_t gc_round, const MsgCurrent& cur,
+                               hipStream_t s) {
   if (b.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_cert_verdict, dim3((uint32_t)((b.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, b,
-                     gc_round);
+                     gc_round, cur);
   return hipGetLastError();
 }
 

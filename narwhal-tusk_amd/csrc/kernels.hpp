@@ -103,6 +103,7 @@ struct CertBufs {
   const uint64_t* moff;  // message i = wire[moff[i] .. moff[i] + mlen[i])
   const uint64_t* mlen;
   uint64_t n;
+  uint32_t kinds;        // the kinds this call decides (msg_plan.hpp kMsgKinds*); the others come back "host"
   uint64_t* round;       // k_cert_parse
   uint32_t *author, *np, *nq, *nv, *flags, *plen;
   uint64_t *vbase, *pbase;  // k_cert_scan (n + 1 entries)
@@ -122,6 +123,13 @@ struct CertBufs {
 hipError_t launch_cert_parse(const CertCommittee& c, const CertBufs& b, hipStream_t s);
 hipError_t launch_cert_scan(const CertBufs& b, hipStream_t s);
 hipError_t launch_cert_scatter(const CertCommittee& c, const CertBufs& b, hipStream_t s);
-hipError_t launch_cert_verdict(const CertCommittee& c, const CertBufs& b, uint64_t gc_round, hipStream_t s);
+// The header currently being voted on (Core::current_header), as a vote's
+// digest preimage spells it: id || round_le || author (18 words), and its round.
+struct MsgCurrent {
+  uint32_t w[18];
+  uint64_t round;
+};
+hipError_t launch_cert_verdict(const CertCommittee& c, const CertBufs& b, uint64_t gc_round, const MsgCurrent& cur,
+                               hipStream_t s);
 
 }  // namespace nt

@@ -601,28 +601,12 @@ struct DeviceCommittee {
   ~DeviceCommittee() { nt_committee_free(cm); }
 };
 
-std::vector<DagError> Core::ingest_device(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
-                                          int threads, size_t* host_decided) const {
-  if (!cache) throw crypto::BackendError("Core::ingest_device needs the committee key cache");
-  nt_ctx* ctx = crypto::Backend::global().ctx();
-  if (!dev_committee) {
-    const Committee& cm = *committee;
-    std::vector<uint32_t> stake, wids;
-    std::vector<uint64_t> wfirst{0};
-    for (const auto& kv : cm.authorities) {
-      stake.push_back(kv.second.stake);
-      wids.insert(wids.end(), kv.second.workers.begin(), kv.second.workers.end());
-      wfirst.push_back(wids.size());
-    }
-    auto d = std::make_shared<DeviceCommittee>();
-    check(nt_committee_create(ctx, cache->handle(), stake.data(), wfirst.data(), wids.data(), cm.quorum_threshold(),
-                              &d->cm),
-          "nt_committee_create");
-    dev_committee = d;
-  }
-  std::vector<uint8_t> code(std::max<size_t>(n, 1));
-  if (n) check(nt_certificates_ingest(ctx, dev_committee->cm, data, off, len, n, gc_round, code.data()),
-               "nt_certificates_ingest");
+namespace {
+
+// the device's codes into DagErrors; the NT_DAG_HOST messages through ingest_soa
+std::vector<DagError> finish_on_host(const Core& core, const std::vector<uint8_t>& code, const uint8_t* data,
+                                     const uint64_t* off, const uint64_t* len, size_t n, int threads,
+                                     size_t* host_decided) {
   std::vector<DagError> res(n, DagError::Ok);
   std::vector<uint64_t> hoff, hlen;
   std::vector<size_t> hidx;
@@ -637,10 +621,53 @@ std::vector<DagError> Core::ingest_device(const uint8_t* data, const uint64_t* o
   }
   if (host_decided) *host_decided = hidx.size();
   if (!hidx.empty()) {
-    const auto r = ingest_soa(data, hoff.data(), hlen.data(), hidx.size(), threads);
+    const auto r = core.ingest_soa(data, hoff.data(), hlen.data(), hidx.size(), threads);
     for (size_t k = 0; k < hidx.size(); ++k) res[hidx[k]] = r[k];
   }
   return res;
+}
+
+// Core::dev_committee, built on first use
+nt_committee* device_committee(const Core& core, nt_ctx* ctx) {
+  if (!core.cache) throw crypto::BackendError("Core: device ingestion needs the committee key cache");
+  if (!core.dev_committee) {
+    const Committee& cm = *core.committee;
+    std::vector<uint32_t> stake, wids;
+    std::vector<uint64_t> wfirst{0};
+    for (const auto& kv : cm.authorities) {
+      stake.push_back(kv.second.stake);
+      wids.insert(wids.end(), kv.second.workers.begin(), kv.second.workers.end());
+      wfirst.push_back(wids.size());
+    }
+    auto d = std::make_shared<DeviceCommittee>();
+    check(nt_committee_create(ctx, core.cache->handle(), stake.data(), wfirst.data(), wids.data(),
+                              cm.quorum_threshold(), &d->cm),
+          "nt_committee_create");
+    core.dev_committee = d;
+  }
+  return core.dev_committee->cm;
+}
+
+}  // namespace
+
+std::vector<DagError> Core::ingest_device(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
+                                          int threads, size_t* host_decided) const {
+  nt_ctx* ctx = crypto::Backend::global().ctx();
+  nt_committee* dc = device_committee(*this, ctx);
+  std::vector<uint8_t> code(std::max<size_t>(n, 1));
+  if (n) check(nt_certificates_ingest(ctx, dc, data, off, len, n, gc_round, code.data()), "nt_certificates_ingest");
+  return finish_on_host(*this, code, data, off, len, n, threads, host_decided);
+}
+
+std::vector<DagError> Core::ingest_device_all(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
+                                              int threads, size_t* host_decided) const {
+  nt_ctx* ctx = crypto::Backend::global().ctx();
+  nt_committee* dc = device_committee(*this, ctx);
+  std::vector<uint8_t> code(std::max<size_t>(n, 1));
+  if (n) check(nt_primary_messages_ingest(ctx, dc, data, off, len, n, gc_round, current_header.id.bytes.data(),
+                                          current_header.round, current_header.author.bytes.data(), code.data()),
+               "nt_primary_messages_ingest");
+  return finish_on_host(*this, code, data, off, len, n, threads, host_decided);
 }
 
 std::vector<DagError> Core::ingest_pipelined(const uint8_t* data, const uint64_t* off, const uint64_t* len,

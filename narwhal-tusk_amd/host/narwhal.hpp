@@ -161,6 +161,12 @@ struct Core {
   // bytes) go through ingest_soa.  Same verdicts as ingest.
   std::vector<DagError> ingest_device(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
                                       int threads = 1, size_t* host_decided = nullptr) const;
+  // ingest_device_all: the whole drain on the GPU (nt_primary_messages_ingest with
+  // current_header's id, round and author): headers, votes and requests are
+  // decided there too; only the NT_DAG_HOST messages (non-canonical or malformed
+  // bytes, keys outside the committee) go through ingest_soa.  Same verdicts.
+  std::vector<DagError> ingest_device_all(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
+                                          int threads = 1, size_t* host_decided = nullptr) const;
   // the batch in chunks of `chunk` messages, two chunks in flight on two
   // workspaces: one chunk's host decode and checks overlap the other's GPU
   // launches.  Same verdicts as ingest (messages are independent).

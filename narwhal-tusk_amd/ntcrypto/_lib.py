@@ -37,6 +37,7 @@ EXPORTED = [
     "nt_committee_create", "nt_committee_free", "nt_certificates_ingest", "nt_small_call_model",
     "nt_set_hbm_budget", "nt_memory_info", "nt_dev_stream", "nt_set_key_cache", "nt_key_cache_add",
     "nt_key_cache_sync", "nt_key_cache_info", "nt_dev_clock_probe", "nt_dev_ed25519_verify_keyset_groups",
+    "nt_primary_messages_ingest",
 ]
 KEY_CACHE_INFO_KEYS = ("keys", "max_keys", "comb_bits", "bytes_per_device", "hits", "misses", "admitted", "refused",
                        "pending", "error", "alloc_us", "build_us")
@@ -101,6 +102,8 @@ def load_library(path=None):
     lib.nt_committee_free.argtypes = [_vp]
     lib.nt_committee_free.restype = None
     lib.nt_certificates_ingest.argtypes = [_vp, _vp, _u8p, _u64p, _u64p, _u64, _u64, _u8p]
+    if hasattr(lib, "nt_primary_messages_ingest"):  # absent from older A/B builds (NTCRYPTO_LIB)
+        lib.nt_primary_messages_ingest.argtypes = [_vp, _vp, _u8p, _u64p, _u64p, _u64, _u64, _u8p, _u64, _u8p, _u8p]
     if hasattr(lib, "nt_memory_info"):  # absent from round-3 A/B builds (NTCRYPTO_LIB)
         lib.nt_set_hbm_budget.argtypes = [_vp, ctypes.c_uint64]
         lib.nt_memory_info.argtypes = [_vp, ctypes.c_int, _u64p]
@@ -464,7 +467,8 @@ def default_backend():
 class Committee:
     """A committee over a keyset (nt_committee_*): stake and worker ids per key,
     the quorum threshold; ingest() runs Certificate::verify on wire bytes on the
-    device (nt_certificates_ingest).  It keeps the keyset's device tables alive:
+    device (nt_certificates_ingest), ingest_messages() Core's checks of every kind
+    of PrimaryMessage (nt_primary_messages_ingest).  It keeps the keyset's device tables alive:
     the Keyset may be closed first."""
 
     def __init__(self, keyset, stakes, workers, quorum):
@@ -479,8 +483,8 @@ class Committee:
                                                _p(wids, _u32p), int(quorum), ctypes.byref(h)), "nt_committee_create")
         self.h = h
 
-    def ingest(self, messages, gc_round=0):
-        """primary::DagError code per wire message (NT_DAG_HOST = 0xff: left to the host decoder)."""
+    @staticmethod
+    def _packed(messages):
         n = len(messages)
         ln = np.array([len(m) for m in messages], np.uint64)
         off = np.zeros(n, np.uint64)
@@ -488,9 +492,31 @@ class Committee:
             off[1:] = np.cumsum(ln)[:-1]
         data = np.frombuffer(b"".join(messages), np.uint8) if n else np.zeros(1, np.uint8)
         data = data if len(data) else np.zeros(1, np.uint8)
-        out = np.zeros(max(n, 1), np.uint8)
+        return data, off, ln, np.zeros(max(n, 1), np.uint8)
+
+    def ingest(self, messages, gc_round=0):
+        """primary::DagError code per wire message (NT_DAG_HOST = 0xff: left to the host decoder)."""
+        n = len(messages)
+        data, off, ln, out = self._packed(messages)
         _check(self.be.lib.nt_certificates_ingest(self.be.ctx, self.h, _p(data), _p(off, _u64p), _p(ln, _u64p), n,
                                                   int(gc_round), _p(out)), "nt_certificates_ingest")
+        return out[:n]
+
+    def ingest_messages(self, messages, gc_round=0, cur_id=None, cur_round=0, cur_author=None):
+        """The whole drain on the device (nt_primary_messages_ingest): headers, votes,
+        certificates and requests.  cur_id / cur_round / cur_author: the header being
+        voted on (32-byte id, round, the author's raw 32-byte key; None = zero bytes).
+        Returns the raw codes, NT_DAG_HOST (0xff) included."""
+        n = len(messages)
+        data, off, ln, out = self._packed(messages)
+        cid = np.frombuffer(bytes(cur_id), np.uint8) if cur_id is not None else None
+        cau = np.frombuffer(bytes(cur_author), np.uint8) if cur_author is not None else None
+        if (cid is not None and len(cid) != 32) or (cau is not None and len(cau) != 32):
+            raise ValueError("cur_id and cur_author are 32 bytes each")
+        _check(self.be.lib.nt_primary_messages_ingest(
+            self.be.ctx, self.h, _p(data), _p(off, _u64p), _p(ln, _u64p), n, int(gc_round),
+            _p(cid) if cid is not None else None, int(cur_round), _p(cau) if cau is not None else None, _p(out)),
+            "nt_primary_messages_ingest")
         return out[:n]
 
     def close(self):

@@ -120,7 +120,10 @@ class Core:
         seconds.  general=True: the object-model decoder (cross-check path).
         device=True: Core::ingest_device -- certificates parsed and checked on the
         GPU from the wire bytes (nt_certificates_ingest), the rest on the host;
-        the second value is then the count of messages the host decided."""
+        the second value is then the count of messages the host decided.
+        device="all": Core::ingest_device_all -- headers, votes and requests are
+        decided on the GPU too (nt_primary_messages_ingest); only irregular bytes
+        are left to the host, counted in the second value."""
         n = len(off)
         codes = np.zeros(max(n, 1), np.int32)
         dec = ctypes.c_double(0)
@@ -130,7 +133,7 @@ class Core:
         rc = load().ntn_core_ingest(self._h, data.ctypes.data_as(_u8p), off.ctypes.data_as(_u64p),
                                     ln.ctypes.data_as(_u64p), n, threads,
                                     codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(dec),
-                                    2 if device else int(general))
+                                    (3 if device == "all" else 2) if device else int(general))
         if rc != 0:
             raise NtError("ntn_core_ingest: backend failure")
         return codes[:n], (int(dec.value) if device else dec.value)
