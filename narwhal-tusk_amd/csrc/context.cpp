@@ -156,8 +156,9 @@ static void xcache_for(Device& dv) {
     const uint64_t bytes = 32ull * slots;
     if (e.budget->reserve_aux(bytes)) {
       void* p = nullptr;
+      hipStream_t s = dv.lane[0].stream;
       if (hipSetDevice(e.ordinal) == hipSuccess && hipMalloc(&p, bytes) == hipSuccess &&
-          hipMemsetAsync(p, 0, bytes, dv.stream) == hipSuccess && hipStreamSynchronize(dv.stream) == hipSuccess) {
+          hipMemsetAsync(p, 0, bytes, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
         e.d_xtab = p;
         e.xslots = slots;
         e.xtab_reserved = bytes;
@@ -175,11 +176,12 @@ static void xcache_for(Device& dv) {
   dv.xtab_ready.store(1, std::memory_order_release);
 }
 
-// everything the verify kernel of slot dv reads besides its inputs
+// everything the verify kernel of slot dv reads besides its inputs; lane 0's [k]A workspace at
+// its full ws_slots slots (before a call's copies start, not at its first launch)
 int verify_tables(Device& dv) {
   NT_CHK(comb_b_for(dv));
   xcache_for(dv);
-  return dv.ensure_ws();
+  return Device::grow_synced(dv.lane[0].ws, nt::ws_bytes_per_slot() * dv.ws_slots, dv.lane[0].ws_done);
 }
 
 // Comb width of a new key set: the widest of 21 (reduced scalars) / 20 / 18 /
@@ -391,10 +393,12 @@ int nt_memory_info(nt_ctx* ctx, int dev, uint64_t* out8) {
   for (auto& x : e.extra) slots.push_back(x.get());
   for (Device* sl : slots) {
     std::lock_guard<std::mutex> lk(sl->mu);
-    ws += (sl->d_ws ? nt::ws_bytes_per_slot() * sl->ws_slots : 0) + sl->ws2.cap;
-    stash += sl->d[B_STASH].cap + sl->d[B_SORT].cap + sl->stash2.cap + sl->sort2.cap;
-    for (int b = 0; b < B_NBUF; ++b)
-      if (b != B_STASH && b != B_SORT) staging += sl->d[b].cap;
+    // ws: both lanes' workspaces; stash: both lanes' stash + sort scratch; staging: all of d[]
+    for (const Lane& l : sl->lane) {
+      ws += l.ws.cap;
+      stash += l.stash.cap + l.sort.cap;
+    }
+    for (const DevBuf& b : sl->d) staging += b.cap;
   }
   uint64_t comb_bits = 0, comb_bytes = 0, reserved = 0;
   {

@@ -4,12 +4,28 @@
 
 using namespace ntrt;
 
+// The key-cache launch of a device-API call on the caller's stream s.  The lanes' scratch is
+// shared with the host entry points, each pair ordered against every other user by its event
+// whatever the streams; successive device-API calls alternate between the lanes (like
+// nt_dev_ed25519_verify's workspaces, on a counter of their own), so batches on two streams
+// can overlap.
+static int keyset_dev(Device& dv, const nt_keyset& ks, hipStream_t s, int mode, const uint32_t* d_key_idx,
+                      const uint8_t* d_sig64, const uint8_t* d_msg, uint64_t msg_bytes, const uint64_t* d_off,
+                      const uint64_t* d_len, uint64_t n, uint64_t* d_out_words, nt::KsGroups groups) {
+  std::lock_guard<std::mutex> lk(dv.mu);
+  NT_CHK(comb_b_for(dv));
+  const nt::KsTabs tabs = ks_tabs(ks.t->dev[dv.group], ks.bits, ks.nkeys, dv);
+  return dv.keyset_on(dv.lane[dv.ks_calls++ & 1], s, n, [&](nt::KsScratch scratch) {
+    return nt::launch_verify_keyset(mode, tabs, scratch, d_key_idx, d_sig64, d_msg, msg_bytes, d_off, d_len, n,
+                                    d_out_words, s, groups);
+  });
+}
+
 extern "C" {
 
 int nt_dev_stream(nt_ctx* ctx, int dev, int which, void** out) {
   if (!ctx || !out || dev < 0 || dev >= (int)ctx->devs.size() || (which != 0 && which != 1)) return NT_EINVAL;
-  Device& d = *ctx->devs[dev];
-  *out = (void*)(which ? d.stream2 : d.stream);
+  *out = (void*)ctx->devs[dev]->lane[which].stream;
   return NT_OK;
 }
 
@@ -43,11 +59,14 @@ int nt_dev_ed25519_verify(nt_ctx* ctx, int dev, void* stream, int mode, const ui
   if (!dv || (mode != NT_MODE_STRICT && mode != NT_MODE_COFACTORLESS)) return NT_EINVAL;
   if (n && (!d_pk32 || !d_sig64 || !d_msg || !d_off || !d_len || !d_out_words)) return NT_EINVAL;
   NT_TRY(hipSetDevice(dv->ordinal));
-  // the [k]A workspaces are per device: launches that use one are ordered by its event
+  // Successive calls alternate between the lanes' [k]A workspaces (each at its full ws_slots
+  // slots), so back-to-back batches issued on two caller streams overlap -- the waves of the
+  // next batch fill the SIMDs the previous batch's last round leaves idle.  Calls on one
+  // stream stay in stream order.
   std::lock_guard<std::mutex> lk(dv->mu);
   NT_CHK(verify_tables(*dv));
-  NT_TRY(dv->verify_dev(mode, d_pk32, d_sig64, d_msg, msg_bytes, d_off, d_len, n, d_out_words, (hipStream_t)stream));
-  return NT_OK;
+  return dv->verify_on(dv->lane[dv->dev_calls++ & 1], (hipStream_t)stream, mode, d_pk32, d_sig64, d_msg, msg_bytes,
+                       d_off, d_len, n, d_out_words, 0, dv->ws_slots);
 }
 
 int nt_dev_group_and(nt_ctx* ctx, int dev, void* stream, const uint64_t* d_first,
@@ -69,23 +88,8 @@ int nt_dev_ed25519_verify_keyset(nt_ctx* ctx, const nt_keyset* ks, int dev, void
     return NT_EINVAL;
   if (n && (!d_key_idx || !d_sig64 || !d_msg || !d_off || !d_len || !d_out_words)) return NT_EINVAL;
   NT_TRY(hipSetDevice(dv->ordinal));
-  hipStream_t s = (hipStream_t)stream;
-  const auto& pd = ks->t->dev[dev];
-  // the device's two stashes, shared with the host entry points, each ordered
-  // against every other user by its event whatever the streams; successive
-  // device-API calls alternate between them (like nt_dev_ed25519_verify's
-  // workspaces), so batches on two streams can overlap
-  std::lock_guard<std::mutex> lk(dv->mu);
-  NT_CHK(comb_b_for(*dv));
-  const int k = (int)(dv->ks_calls++ & 1u);
-  NT_CHK(dv->ensure_stash(k, n));
-  void* stash = k ? dv->stash2.p : dv->d[B_STASH].p;
-  void* so = k ? dv->sort2.p : dv->d[B_SORT].p;
-  return dv->keyset_launch(s, stash, [&] {
-    return nt::launch_verify_keyset(mode, ks->bits, d_key_idx, d_sig64, d_msg, msg_bytes, d_off, d_len, n, pd.d_meta,
-                                    pd.d_enc, pd.d_comb, ks->nkeys, dv->d_combB, dv->bbits, stash, so, d_out_words,
-                                    dv->cus, s);
-  });
+  return keyset_dev(*dv, *ks, (hipStream_t)stream, mode, d_key_idx, d_sig64, d_msg, msg_bytes, d_off, d_len, n,
+                    d_out_words, {});
 }
 
 int nt_dev_clock_probe(nt_ctx* ctx, int dev, void* stream, uint32_t iters, uint64_t* d_out2, uint64_t* wall_khz) {
@@ -116,18 +120,8 @@ int nt_dev_ed25519_verify_keyset_groups(nt_ctx* ctx, const nt_keyset* ks, int de
   if (n == 0) return G ? (nt::launch_group_and(d_first, d_cnt, G, d_out_words, d_group_words, s) == hipSuccess
                               ? NT_OK : NT_EHIP)
                        : NT_OK;
-  const auto& pd = ks->t->dev[dev];
-  std::lock_guard<std::mutex> lk(dv->mu);
-  NT_CHK(comb_b_for(*dv));
-  const int k = (int)(dv->ks_calls++ & 1u);
-  NT_CHK(dv->ensure_stash(k, n));
-  void* stash = k ? dv->stash2.p : dv->d[B_STASH].p;
-  void* so = k ? dv->sort2.p : dv->d[B_SORT].p;
-  return dv->keyset_launch(s, stash, [&] {
-    return nt::launch_verify_keyset(mode, ks->bits, d_key_idx, d_sig64, d_msg, msg_bytes, d_off, d_len, n, pd.d_meta,
-                                    pd.d_enc, pd.d_comb, ks->nkeys, dv->d_combB, dv->bbits, stash, so, d_out_words,
-                                    dv->cus, s, d_first, d_cnt, G, d_group_words);
-  });
+  return keyset_dev(*dv, *ks, s, mode, d_key_idx, d_sig64, d_msg, msg_bytes, d_off, d_len, n, d_out_words,
+                    nt::KsGroups{d_first, d_cnt, G, d_group_words});
 }
 
 int nt_dev_ed25519_sign(nt_ctx* ctx, int dev, void* stream, const uint8_t* d_seed32, const uint8_t* d_msg,

@@ -143,7 +143,7 @@ class GroupShardRun {
   // header digests from pageable memory go through the pinned staging too (32 B
   // per group): a copy from pageable memory returns only when it is done
   bool msg_direct = false;
-  const KsTables::PerDev* pd = nullptr;
+  nt::KsTabs tabs{};  // of a.kd on this slot
   uint8_t *hkey = nullptr, *hsig = nullptr, *hmsg = nullptr;
   const uint64_t* hfirst = nullptr;  // = p.start, in pinned memory
   uint32_t* hcnt = nullptr;
@@ -188,9 +188,8 @@ class GroupShardRun {
     NT_CHK(dv.d[B_OUT].ensure(p.sw * 8 + 8));
     NT_CHK(dv.d[B_OUT2].ensure(p.gw * 8));
     if (a.kd) {
-      NT_CHK(dv.ensure_stash(0, p.max_chunk));
-      if (p.chunks() > 1) NT_CHK(dv.ensure_stash(1, p.max_chunk));
-      pd = &a.kd->t->dev[dv.group];
+      for (size_t k = 0; k < std::min<size_t>(p.chunks(), 2); ++k) NT_CHK(dv.ensure_scratch(dv.lane[k], p.max_chunk));
+      tabs = ks_tabs(a.kd->t->dev[dv.group], a.kd->bits, a.kd->nkeys, dv);
     }
     hkey = dv.h[B_PK].as<uint8_t>();
     hsig = dv.h[B_SIG].as<uint8_t>();
@@ -274,15 +273,12 @@ class GroupShardRun {
       NT_TRY(nt::launch_group_msgs(dfirst, dcnt, ng, doff, dlen, s));
       if (a.kd) {
         // the key-cache launch ANDs the chunk's groups itself (its kernel's epilogue)
-        void* st = (c & 1) ? dv.stash2.p : dv.d[B_STASH].p;
-        void* so = (c & 1) ? dv.sort2.p : dv.d[B_SORT].p;
-        return dv.keyset_launch(s, st, [&] {
-          return nt::launch_verify_keyset(NT_MODE_COFACTORLESS, a.kd->bits, (const uint32_t*)dk, dsig, dmsg, 32 * ng,
-                                          doff, dlen, mc, pd->d_meta, pd->d_enc, pd->d_comb, a.kd->nkeys, dv.d_combB,
-                                          dv.bbits, st, so, dout, dv.cus, s, dfirst, dcnt, ng, dgout);
+        return dv.keyset_on(dv.lane[c & 1], s, p.max_chunk, [&](nt::KsScratch scratch) {
+          return nt::launch_verify_keyset(NT_MODE_COFACTORLESS, tabs, scratch, (const uint32_t*)dk, dsig, dmsg, 32 * ng,
+                                          doff, dlen, mc, dout, s, nt::KsGroups{dfirst, dcnt, ng, dgout});
         });
       }
-      NT_CHK(dv.verify_chunk((int)c, NT_MODE_COFACTORLESS, dk, dsig, dmsg, 32 * ng, doff, dlen, mc, dout));
+      NT_CHK(dv.verify_host(c, NT_MODE_COFACTORLESS, dk, dsig, dmsg, 32 * ng, doff, dlen, mc, dout));
     }
     NT_TRY(nt::launch_group_and(dfirst, dcnt, ng, dout, dgout, s));
     return NT_OK;
@@ -296,10 +292,10 @@ class GroupShardRun {
     NT_CHK(finish_chunks(dv));
     ahead.join();  // every chunk's lookups are done: miss_c is final
     for (auto& v : miss_c) miss.insert(miss.end(), v.begin(), v.end());
-    NT_TRY(hipMemcpyAsync(gbits(), dv.d[B_OUT2].p, p.gw * 8, hipMemcpyDeviceToHost, dv.stream));
+    NT_TRY(hipMemcpyAsync(gbits(), dv.d[B_OUT2].p, p.gw * 8, hipMemcpyDeviceToHost, dv.lane[0].stream));
     if ((a.out_sig_bitmap || !miss.empty()) && p.m)
-      NT_TRY(hipMemcpyAsync(sbits(), dv.d[B_OUT].p, p.sw * 8, hipMemcpyDeviceToHost, dv.stream));
-    NT_TRY(hipStreamSynchronize(dv.stream));
+      NT_TRY(hipMemcpyAsync(sbits(), dv.d[B_OUT].p, p.sw * 8, hipMemcpyDeviceToHost, dv.lane[0].stream));
+    NT_TRY(hipStreamSynchronize(dv.lane[0].stream));
     return NT_OK;
   }
 
@@ -308,7 +304,7 @@ class GroupShardRun {
   // their bits set and their groups' verdicts recomputed on the host
   int resolve_misses() {
     const uint64_t M = miss.size();
-    hipStream_t s = dv.stream;
+    hipStream_t s = dv.lane[0].stream;
     a.nmiss += M;
     NT_CHK(verify_tables(dv));
     NT_CHK(dv.h[B_PK].ensure(M * 32));
@@ -332,9 +328,9 @@ class GroupShardRun {
     NT_TRY(hipMemcpyAsync(dv.d[B_SIG].p, sg, M * 64, hipMemcpyHostToDevice, s));
     NT_TRY(hipMemcpyAsync(dv.d[B_OFF].p, ol, M * 16, hipMemcpyHostToDevice, s));
     const uint64_t R1 = nt::verify_round_sigs(dv.cus, 1);
-    NT_CHK(dv.verify_chunk(0, NT_MODE_COFACTORLESS, dv.d[B_PK].as<uint8_t>(), dv.d[B_SIG].as<uint8_t>(),
-                           dv.d[B_DATA].as<uint8_t>(), 32 * p.groups(), dv.d[B_OFF].as<uint64_t>(),
-                           dv.d[B_OFF].as<uint64_t>() + M, M, dv.d[B_OUT2].as<uint64_t>(), M <= R1 ? 1 : 0));
+    NT_CHK(dv.verify_host(0, NT_MODE_COFACTORLESS, dv.d[B_PK].as<uint8_t>(), dv.d[B_SIG].as<uint8_t>(),
+                          dv.d[B_DATA].as<uint8_t>(), 32 * p.groups(), dv.d[B_OFF].as<uint64_t>(),
+                          dv.d[B_OFF].as<uint64_t>() + M, M, dv.d[B_OUT2].as<uint64_t>(), M <= R1 ? 1 : 0));
     std::vector<uint64_t> mw((M + 63) / 64);
     NT_TRY(hipMemcpyAsync(mw.data(), dv.d[B_OUT2].p, mw.size() * 8, hipMemcpyDeviceToHost, s));
     NT_TRY(hipStreamSynchronize(s));

@@ -70,26 +70,15 @@ constexpr uint64_t kSlack = 64;  // readable bytes before / after the wire bytes
 struct Side {  // device buffers of one chunk parity, grow-only
   DevBuf wire, moff, mlen, round, u32s, scans, mbase, keys, sigs, smsg, sha, grp, words, code;
   HostBuf tot;
-  hipEvent_t ev = nullptr;
+  hipEvent_t ev = nullptr;  // the chunk's front half is done, its totals in `tot`
+  ~Side() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
 };
 
-struct IngestState {
-  int ordinal = -1;
+struct IngestState {  // goes with its slot (~Device has set the device)
   Side side[2];
   HostBuf hoff, hlen, hcode;
-  ~IngestState() {
-    if (ordinal < 0) return;
-    (void)hipSetDevice(ordinal);
-    for (auto& s : side) {
-      for (DevBuf* b : {&s.wire, &s.moff, &s.mlen, &s.round, &s.u32s, &s.scans, &s.mbase, &s.keys, &s.sigs, &s.smsg,
-                        &s.sha, &s.grp, &s.words, &s.code})
-        if (b->p) (void)hipFree(b->p);
-      if (s.tot.p) (void)hipHostFree(s.tot.p);
-      if (s.ev) (void)hipEventDestroy(s.ev);
-    }
-    for (HostBuf* b : {&hoff, &hlen, &hcode})
-      if (b->p) (void)hipHostFree(b->p);
-  }
 };
 
 // grow a buffer the stream's earlier work may still use: wait for it first
@@ -274,9 +263,10 @@ int ingest_front(Device& dv, IngestState& S, Side& sd, Chunk& ch, const nt_commi
   return NT_OK;
 }
 
-int ingest_back(Device& dv, IngestState& S, Side& sd, int parity, Chunk& ch, const nt_committee& cm,
-                const nt_committee::PerDev& pd, const IngestRules& rules, hipStream_t s) {
+int ingest_back(Device& dv, IngestState& S, Side& sd, Lane& lane, Chunk& ch, const nt_committee& cm,
+                const nt_committee::PerDev& pd, const IngestRules& rules) {
   const uint64_t m = ch.b - ch.a;
+  hipStream_t s = lane.stream;
   NT_TRY(hipEventSynchronize(sd.ev));
   const uint64_t V = sd.tot.as<uint64_t>()[0], P = sd.tot.as<uint64_t>()[1];
   if (V > ch.vmax) return NT_EHIP;  // k_cert_parse bounds every count by the message length
@@ -299,15 +289,12 @@ int ingest_back(Device& dv, IngestState& S, Side& sd, int parity, Chunk& ch, con
   const uint64_t mbytes = 168 * m + 16 + P;  // the preimages and digests k_cert_scatter wrote
   NT_TRY(nt::launch_sha512_trunc32(b.mbase, mbytes, b.soff, b.slen, 2 * m, b.mbase + 32 * m, s,
                                    std::max<uint64_t>(ch.lmax, 72)));
-  NT_CHK0(dv.ensure_stash(parity, nsig));
-  void* st = parity ? dv.stash2.p : dv.d[B_STASH].p;
-  void* so = parity ? dv.sort2.p : dv.d[B_SORT].p;
-  const auto& kd = cm.kt->dev[dv.group];
-  NT_CHK0(dv.keyset_launch(s, st, [&] {
-    return nt::launch_verify_keyset(NT_MODE_MIXED, cm.kt->bits, b.keys, (const uint8_t*)b.sigs, b.mbase, mbytes, b.smoff,
-                                    b.smlen, nsig, kd.d_meta, kd.d_enc, kd.d_comb, cm.kt->nkeys, dv.d_combB, dv.bbits,
-                                    st, so, sd.words.as<uint64_t>(), dv.cus, s, b.gfirst, b.gcnt, m,
-                                    (uint64_t*)b.grp_words);  // the vote groups' AND in the kernel's epilogue
+  const nt::KsTabs tabs = ks_tabs(cm.kt->dev[dv.group], cm.kt->bits, cm.kt->nkeys, dv);
+  // the vote groups' AND in the kernel's epilogue
+  NT_CHK0(dv.keyset_on(lane, s, nsig, [&](nt::KsScratch scratch) {
+    return nt::launch_verify_keyset(NT_MODE_MIXED, tabs, scratch, b.keys, (const uint8_t*)b.sigs, b.mbase, mbytes,
+                                    b.smoff, b.smlen, nsig, sd.words.as<uint64_t>(), s,
+                                    nt::KsGroups{b.gfirst, b.gcnt, m, (uint64_t*)b.grp_words});
   }));
   NT_TRY(nt::launch_cert_verdict(pd.c, b, rules.gc_round, rules.cur, s));
   NT_TRY(hipMemcpyAsync(S.hcode.as<uint8_t>() + ch.a, b.code, m, hipMemcpyDeviceToHost, s));
@@ -321,14 +308,12 @@ int ingest_shard(Device& dv, const nt_committee& cm, const uint8_t* data, const 
   NT_CHK0(comb_b_for(dv));
   if (!dv.ingest) {
     auto st = std::make_shared<IngestState>();
-    st->ordinal = dv.ordinal;
     for (auto& sd : st->side) NT_TRY(hipEventCreateWithFlags(&sd.ev, hipEventDisableTiming));
     dv.ingest = st;
   }
   IngestState& S = *(IngestState*)dv.ingest.get();
   // both compute streams must be idle before the shared host staging is rewritten
-  NT_TRY(hipStreamSynchronize(dv.stream));
-  NT_TRY(hipStreamSynchronize(dv.stream2));
+  for (Lane& l : dv.lane) NT_TRY(hipStreamSynchronize(l.stream));
   NT_CHK0(S.hoff.ensure(n * 8));
   NT_CHK0(S.hlen.ensure(n * 8));
   NT_CHK0(S.hcode.ensure(n));
@@ -346,11 +331,9 @@ int ingest_shard(Device& dv, const nt_committee& cm, const uint8_t* data, const 
   const uint64_t* l = len + lo;
   for (size_t k = 0; k <= ch.size(); ++k) {
     if (k < ch.size()) NT_CHK0(ingest_front(dv, S, S.side[k & 1], ch[k], pd, d, o, l, rules.kinds, dv.cstr((int)k)));
-    if (k >= 1) NT_CHK0(ingest_back(dv, S, S.side[(k - 1) & 1], (int)((k - 1) & 1), ch[k - 1], cm, pd, rules,
-                                    dv.cstr((int)(k - 1))));
+    if (k >= 1) NT_CHK0(ingest_back(dv, S, S.side[(k - 1) & 1], dv.lane[(k - 1) & 1], ch[k - 1], cm, pd, rules));
   }
-  NT_TRY(hipStreamSynchronize(dv.stream));
-  NT_TRY(hipStreamSynchronize(dv.stream2));
+  for (Lane& l : dv.lane) NT_TRY(hipStreamSynchronize(l.stream));
   std::memcpy(out + lo, S.hcode.p, n);
   return NT_OK;
 }

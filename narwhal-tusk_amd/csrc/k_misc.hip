@@ -718,12 +718,18 @@ static bool keyset_fuse() {
   return on;
 }
 
-hipError_t launch_verify_keyset(int mode, int key_bits, const uint32_t* d_key_idx, const uint8_t* d_sig, const uint8_t* d_msg,
-                                uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n, const uint32_t* d_meta,
-                                const uint32_t* d_enc, const uint32_t* d_combA, uint32_t nkeys,
-                                const uint32_t* d_combB, int bbits, void* d_stash, void* d_sort, uint64_t* d_out_words,
-                                uint32_t cus, hipStream_t s, const uint64_t* d_gfirst, const uint32_t* d_gcnt, uint64_t G,
-                                uint64_t* d_group_words) {
+hipError_t launch_verify_keyset(int mode, const KsTabs& tabs, KsScratch scratch, const uint32_t* d_key_idx,
+                                const uint8_t* d_sig, const uint8_t* d_msg, uint64_t msg_bytes, const uint64_t* d_off,
+                                const uint64_t* d_len, uint64_t n, uint64_t* d_out_words, hipStream_t s,
+                                KsGroups groups) {
+  const int key_bits = tabs.key_bits, bbits = tabs.bbits;
+  const uint32_t *d_meta = tabs.meta, *d_enc = tabs.enc, *d_combA = tabs.combA, *d_combB = tabs.combB;
+  const uint32_t nkeys = tabs.nkeys, cus = tabs.cus;
+  void *d_stash = scratch.stash, *d_sort = scratch.sort;
+  const uint64_t* d_gfirst = groups.first;
+  const uint32_t* d_gcnt = groups.cnt;
+  const uint64_t G = groups.G;
+  uint64_t* d_group_words = groups.words;
   if (!d_sort || !d_stash || !d_combB) return hipErrorInvalidValue;
   if (bbits != kBCombBits && bbits != kBCombFallback) return hipErrorInvalidValue;
   if (G && (!d_gfirst || !d_gcnt || !d_group_words)) return hipErrorInvalidValue;

@@ -58,14 +58,14 @@ int keyset_create(nt_ctx* ctx, const uint8_t* pk32, uint32_t nkeys, int bits, nt
       return NT_ENOMEM;
     }
     if (nkeys) {
-      NT_TRY(hipMemcpyAsync(pd.d_enc, pk32, 32ull * nkeys, hipMemcpyHostToDevice, dv.stream));
-      NT_TRY(hipStreamSynchronize(dv.stream));
+      NT_TRY(hipMemcpyAsync(pd.d_enc, pk32, 32ull * nkeys, hipMemcpyHostToDevice, dv.lane[0].stream));
+      NT_TRY(hipStreamSynchronize(dv.lane[0].stream));
       const int rc = dv.build_wcombs(ks->bits, (const uint32_t*)pk32, nkeys, 1, pd.d_comb, pd.d_meta);
       if (rc != NT_OK) return rc;
       if (di == 0)
-        NT_TRY(hipMemcpyAsync(ks->flags.data(), pd.d_meta, 4ull * nkeys, hipMemcpyDeviceToHost, dv.stream));
+        NT_TRY(hipMemcpyAsync(ks->flags.data(), pd.d_meta, 4ull * nkeys, hipMemcpyDeviceToHost, dv.lane[0].stream));
     }
-    NT_TRY(hipStreamSynchronize(dv.stream));
+    NT_TRY(hipStreamSynchronize(dv.lane[0].stream));
   }
   *out = ks.release();
   return NT_OK;

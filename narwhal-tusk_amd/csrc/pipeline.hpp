@@ -287,10 +287,10 @@ class LookAhead {
   std::atomic<bool> stop_{false};
 };
 
-// both compute streams drained (host-side), so work issued next on dv.stream
+// both compute streams drained (host-side), so work issued next on lane 0's stream
 // follows every chunk's kernels without a cross-queue wait
 inline int finish_chunks(Device& dv) {
-  if (dv.stream2 != dv.stream) NT_TRY(hipStreamSynchronize(dv.stream2));
+  if (dv.lane[1].stream != dv.lane[0].stream) NT_TRY(hipStreamSynchronize(dv.lane[1].stream));
   return NT_OK;
 }
 

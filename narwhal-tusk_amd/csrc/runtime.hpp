@@ -3,6 +3,12 @@
 // keyset.cpp, sign.cpp, dev_api.cpp: one per family of entry points;
 // registry.cpp: the key registry; ingest_gpu.cpp: wire ingestion on the
 // device).  Not part of the ABI.
+//
+// A context (nt_ctx) holds one Device per device entry; an entry holds extra
+// execution slots (Devices too) that share its tables.  A slot's per-stream state
+// is its two Lanes: every uncached verify launch goes through Device::verify_on
+// and every key-cache launch through Device::keyset_on, which order the lane's
+// scratch by its event.  Buffers (DevBuf / HostBuf) own their memory.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -39,48 +45,52 @@ struct KeyReg;
     if (_rc != NT_OK) return _rc; \
   } while (0)
 
-struct DevBuf {
+// A grow-only buffer in device memory (DevBuf) or pinned host memory (HostBuf) that owns its
+// allocation: move-only, freed with the object.  ensure() keeps a buffer that is large enough
+// and otherwise replaces it (the contents are lost) by one of at least 64 KB, rounded up to
+// 4 KB; a failed allocation leaves it empty, returns NT_ENOMEM and clears HIP's sticky error.
+template <bool kHost>
+struct Buf {
   void* p = nullptr;
   size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return NT_OK;
-    if (p) (void)hipFree(p);
+  Buf() = default;
+  Buf(Buf&& o) noexcept { *this = std::move(o); }
+  Buf& operator=(Buf&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~Buf() { release(); }
+  void release() {
+    if (p) (void)(kHost ? hipHostFree(p) : hipFree(p));
     p = nullptr;
     cap = 0;
+  }
+  int ensure(size_t bytes) {
+    if (bytes <= cap) return NT_OK;
+    release();
     size_t want = std::max<size_t>(bytes, 1 << 16);
     want = (want + 4095) & ~(size_t)4095;
-    if (hipMalloc(&p, want) != hipSuccess) return NT_ENOMEM;
+    if ((kHost ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return NT_ENOMEM;
+    }
     cap = want;
     return NT_OK;
   }
   template <class T>
   T* as() const { return (T*)p; }
 };
-
-struct HostBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return NT_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = std::max<size_t>(bytes, 1 << 16);
-    want = (want + 4095) & ~(size_t)4095;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return NT_ENOMEM;
-    cap = want;
-    return NT_OK;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
+using DevBuf = Buf<false>;
+using HostBuf = Buf<true>;
 
 // nt_host_alloc registry: [base, base + bytes) of every live pinned buffer (context.cpp)
 extern std::mutex g_pin_mu;
 extern std::map<uintptr_t, uint64_t> g_pinned;
 bool is_pinned(const void* p, uint64_t bytes);
 
-enum { B_DATA, B_OFF, B_LEN, B_PK, B_SIG, B_OUT, B_OUT2, B_FIRST, B_CNT, B_STASH, B_SORT, B_NBUF };
+enum { B_DATA, B_OFF, B_LEN, B_PK, B_SIG, B_OUT, B_OUT2, B_FIRST, B_CNT, B_NBUF };  // staging buffers of a slot
 
 // The wide comb of B of one digit width on one device ordinal, shared by every
 // device entry of every context of the process that runs on that ordinal at
@@ -172,6 +182,19 @@ inline hipError_t compute_stream(hipStream_t* s, uint32_t cus, int which) {
   return hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data());
 }
 
+// One compute stream of an execution slot and the scratch of the launches that alternate onto
+// it: host chunk c runs on lane[c & 1], successive device-API calls take the lanes in turn
+// (on the caller's stream).  Each buffer has an event that its every launch waits on and
+// records, whatever stream the launch runs on, so two users of one buffer never overlap while
+// the two lanes do.  Grow-only; nothing is allocated at nt_init.
+struct Lane {
+  hipStream_t stream = nullptr;
+  DevBuf ws;          // [k]A workspace of the uncached verify kernel
+  hipEvent_t ws_done = nullptr;
+  DevBuf stash, sort;  // key-cache stash + key-grouping scratch (nt::KsScratch)
+  hipEvent_t stash_done = nullptr;
+};
+
 struct Device {
   int ordinal = -1;
   int group = -1;               // index of this device entry in nt_ctx::devs (keyset tables)
@@ -180,11 +203,9 @@ struct Device {
   std::mutex tables_mu;         // (entry) lazy creation of the comb of B
   std::shared_ptr<CombB> combB;  // holds d_combB (shared per ordinal and width, see CombB); null until first needed
   uint64_t comb_reserved = 0;   // (entry) bytes of the comb of B reserved in the budget
-  hipStream_t stream = nullptr;
   uint32_t* d_combB = nullptr;  // wide comb of B (verify, key-cache verify, sign): comb_b_for() sets it
   int bbits = 0;                // its digit width (nt::kBCombBits or nt::kBCombFallback)
   std::atomic<int> comb_ready{0};  // this slot's d_combB / bbits are set (comb_b_for's lock-free fast path)
-  void* d_ws = nullptr;         // verify workspace: ensure_ws() on the first verify
   // The x cache (ed25519_ops.hpp XCache): uint4 xtab[xslots][2], one table per device entry,
   // shared by its execution slots and both workspaces; xcache_for() (context.cpp) allocates it
   // zero-filled with the first verify and hands every slot the entry's pointer.  Null = none
@@ -197,19 +218,15 @@ struct Device {
   uint32_t ws_slots = 0;
   uint32_t sign_blocks = 0;
   uint32_t cus = 0;
-  hipEvent_t ws_done = nullptr;  // orders every kernel that uses d_ws, whatever its stream
-  hipEvent_t stash_done = nullptr;  // same for the key-cache stash d[B_STASH] (host and device API)
   // host entry points: chunk c's H2D copies go on cstream, cev[c] marks them
   // done, and the host launches chunk c's kernels once it has waited for cev[c]
   // (pipeline.hpp run_chunks), so copies of chunk c+1 overlap kernels of chunk c
   hipStream_t cstream = nullptr;
   hipEvent_t cev[16] = {};
-  // ... and chunks alternate between two compute streams, so the waves of chunk
-  // c+1 fill the CUs that chunk c's last waves leave idle.  Stream 2 has its own
-  // verify workspace and key-cache stash.
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ws2_done = nullptr, stash2_done = nullptr;
-  DevBuf ws2, stash2, sort2;
+  // ... and chunks alternate between the two lanes, so the waves of chunk c+1
+  // fill the CUs that chunk c's last waves leave idle.  Work that is not chunked
+  // (table builds, read-backs, signing) runs on lane[0].stream.
+  Lane lane[2];
   std::mutex mu;
   uint64_t dev_calls = 0;  // device-API verify calls (workspace alternation), under mu
   uint64_t ks_calls = 0;   // device-API key-cache calls (stash alternation), under mu
@@ -225,33 +242,24 @@ struct Device {
   // state of the wire-ingestion entry point on this slot (ingest_gpu.cpp), created on first use
   std::shared_ptr<void> ingest;
 
+  // The buffers free themselves (after this body).  What needs an order: the streams drained
+  // first, and the extra slots gone before this entry's comb of B and x table, which they borrow.
   ~Device() {
     if (comb_reserved && budget) budget->release(comb_reserved);
     if (xtab_reserved && budget) budget->release_aux(xtab_reserved);
     if (ordinal < 0) return;
     (void)hipSetDevice(ordinal);
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (auto& b : d)
-      if (b.p) (void)hipFree(b.p);
-    for (auto& b : h)
-      if (b.p) (void)hipHostFree(b.p);
-    extra.clear();  // before this entry's comb, which the extra slots borrow
-    (void)hipSetDevice(ordinal);
-    if (d_ws) (void)hipFree(d_ws);
-    if (ws_done) (void)hipEventDestroy(ws_done);
-    if (stash_done) (void)hipEventDestroy(stash_done);
+    for (Lane& l : lane)
+      if (l.stream) (void)hipStreamSynchronize(l.stream);
+    extra.clear();
+    if (entry == this && d_xtab) (void)hipFree(d_xtab);
+    for (hipEvent_t e : {lane[0].ws_done, lane[0].stash_done, lane[1].ws_done, lane[1].stash_done})
+      if (e) (void)hipEventDestroy(e);
     for (auto& e : cev)
       if (e) (void)hipEventDestroy(e);
-    if (stream2 && stream2 != stream) (void)hipStreamSynchronize(stream2);
-    if (entry == this && d_xtab) (void)hipFree(d_xtab);
-    if (ws2.p) (void)hipFree(ws2.p);
-    if (stash2.p) (void)hipFree(stash2.p);
-    if (sort2.p) (void)hipFree(sort2.p);
-    if (ws2_done) (void)hipEventDestroy(ws2_done);
-    if (stash2_done) (void)hipEventDestroy(stash2_done);
-    if (stream2 && stream2 != stream) (void)hipStreamDestroy(stream2);
-    if (cstream && cstream != stream) (void)hipStreamDestroy(cstream);
-    if (stream) (void)hipStreamDestroy(stream);
+    for (hipStream_t s : {cstream, lane[1].stream})
+      if (s && s != lane[0].stream) (void)hipStreamDestroy(s);
+    if (lane[0].stream) (void)hipStreamDestroy(lane[0].stream);
   }
 
   int init(int ord, int grp, Device* share = nullptr) {
@@ -265,27 +273,28 @@ struct Device {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return NT_ENODEV;
     if (share) {
       // an extra (latency) slot: ONE stream at the highest priority for its
-      // copies and kernels, so it does not share a hardware queue with the
-      // bulk streams of the entry's first slot (HIP multiplexes a process's
-      // streams over GPU_MAX_HW_QUEUES = 4 queues; a kernel behind a 17 ms
-      // digest flush in the same queue waits for it)
+      // copies and kernels (both lanes share it; each keeps its own scratch),
+      // so it does not share a hardware queue with the bulk streams of the
+      // entry's first slot (HIP multiplexes a process's streams over
+      // GPU_MAX_HW_QUEUES = 4 queues; a kernel behind a 17 ms digest flush in
+      // the same queue waits for it)
       int lo = 0, hi = 0;
       NT_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      NT_TRY(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi));
-      cstream = stream2 = stream;
+      NT_TRY(hipStreamCreateWithPriority(&lane[0].stream, hipStreamNonBlocking, hi));
+      cstream = lane[1].stream = lane[0].stream;
     } else {
       // the two compute streams (compute_stream)
-      NT_TRY(compute_stream(&stream, (uint32_t)prop.multiProcessorCount, 0));
+      NT_TRY(compute_stream(&lane[0].stream, (uint32_t)prop.multiProcessorCount, 0));
       NT_TRY(hipStreamCreateWithFlags(&cstream, hipStreamNonBlocking));
-      NT_TRY(compute_stream(&stream2, (uint32_t)prop.multiProcessorCount, 1));
+      NT_TRY(compute_stream(&lane[1].stream, (uint32_t)prop.multiProcessorCount, 1));
     }
-    NT_TRY(hipEventCreateWithFlags(&ws_done, hipEventDisableTiming));
-    NT_TRY(hipEventCreateWithFlags(&stash_done, hipEventDisableTiming));
+    for (hipEvent_t* e : {&lane[0].ws_done, &lane[0].stash_done, &lane[1].ws_done, &lane[1].stash_done}) {
+      NT_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      NT_TRY(hipEventRecord(*e, lane[0].stream));
+    }
     for (auto& e : cev) NT_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    NT_TRY(hipEventCreateWithFlags(&ws2_done, hipEventDisableTiming));
-    NT_TRY(hipEventCreateWithFlags(&stash2_done, hipEventDisableTiming));
-    // Nothing large is allocated here: the comb of B and the verify workspace
-    // come with the first call that needs them (comb_b_for, ensure_ws).
+    // Nothing large is allocated here: the comb of B and the verify workspaces
+    // come with the first call that needs them (comb_b_for, verify_tables, verify_on).
     // Workspace slots = grid cap of the verify kernel.  Four times the resident
     // workgroups (256-thread blocks, `occupancy` waves per SIMD, 4 SIMDs per CU):
     // up to 2M signatures per launch the grid is then one 512-signature block per
@@ -296,22 +305,18 @@ struct Device {
     ws_slots = slots;
     sign_blocks = (uint32_t)prop.multiProcessorCount * 8;
     cus = (uint32_t)prop.multiProcessorCount;
-    NT_TRY(hipEventRecord(ws_done, stream));
-    NT_TRY(hipEventRecord(stash_done, stream));
-    NT_TRY(hipEventRecord(ws2_done, stream));
-    NT_TRY(hipEventRecord(stash2_done, stream));
-    NT_TRY(hipStreamSynchronize(stream));
+    NT_TRY(hipStreamSynchronize(lane[0].stream));
     return NT_OK;
   }
 
   // Wide combs of nkeys encoded points (host words) into d_comb (device);
   // negate: comb of -P (committee keys) instead of P (the base point).
-  // s: the stream the build runs on (null = the slot's `stream`; the key
+  // s: the stream the build runs on (null = lane[0].stream; the key
   // registry's admissions pass a low-priority stream of their own)
   int build_wcombs(int bits, const uint32_t* enc_host, uint32_t nkeys, int negate, uint32_t* d_comb, uint32_t* d_meta,
                    hipStream_t s = nullptr) {
     if (nkeys == 0) return NT_OK;
-    if (!s) s = stream;
+    if (!s) s = lane[0].stream;
     const uint32_t batch = std::min<uint32_t>(nkeys, nt::wcomb_fill_batch(bits));
     uint32_t *d_enc = nullptr, *d_bases = nullptr, *d_tmp = nullptr;
     int rc = NT_OK;
@@ -331,18 +336,6 @@ struct Device {
     return rc;
   }
 
-  // the [k]A workspace of the verify kernel (ws_slots x 737 KB, ~1.5 GB at
-  // 2,048 slots), on the slot's first verify
-  int ensure_ws() {
-    if (d_ws) return NT_OK;
-    if (hipMalloc(&d_ws, nt::ws_bytes_per_slot() * ws_slots) != hipSuccess) {
-      (void)hipGetLastError();
-      d_ws = nullptr;
-      return NT_ENOMEM;
-    }
-    return NT_OK;
-  }
-
   // The x cache as a launch sees it.  NT_XCACHE_SLOTS is read again at every launch: a value
   // below the allocated size confines the launch to the table's first slots (0: no cache for
   // this launch), a larger one changes nothing.
@@ -359,96 +352,60 @@ struct Device {
   }
 
   // compute stream of chunk c
-  hipStream_t cstr(int c) const { return (c & 1) ? stream2 : stream; }
+  hipStream_t cstr(int c) const { return lane[c & 1].stream; }
 
-  // verify launch of chunk c: even chunks use the device workspace on `stream`,
-  // odd chunks stream2's own workspace (grown to the chunk's grid); per_lane as
-  // in nt::launch_verify
-  int verify_chunk(int c, int mode, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint64_t msg_bytes,
-                   const uint64_t* off, const uint64_t* len, uint64_t n, uint64_t* out, int per_lane = 0) {
-    if (!(c & 1))
-      return verify(mode, pk, sig, msg, msg_bytes, off, len, n, out, stream, per_lane) == hipSuccess ? NT_OK : NT_EHIP;
-    const uint64_t blocks = nt::verify_grid(n, ws_slots, per_lane);
-    const int rc = grow_ws2(blocks);
-    if (rc != NT_OK) return rc;
-    if (hipStreamWaitEvent(stream2, ws2_done, 0) != hipSuccess ||
-        nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, ws2.p,
-                          (uint32_t)std::max<uint64_t>(blocks, 1), out, stream2, per_lane, xtab()) != hipSuccess ||
-        hipEventRecord(ws2_done, stream2) != hipSuccess)
-      return NT_EHIP;
-    return NT_OK;
-  }
-
-  // Key-cache launch on stream s with stash st: every launch waits for the
-  // previous user of its stash (d[B_STASH]: stash_done, stash2: stash2_done --
-  // host chunks on `stream` / stream2 and device-API calls on any stream) and
-  // marks it, like the [k]A workspaces.  The key-grouping scratch (d[B_SORT] /
-  // sort2) goes with its stash.
-  template <class F>
-  int keyset_launch(hipStream_t s, void* st, F&& launch) {
-    const hipEvent_t ev = st == d[B_STASH].p ? stash_done : (st == stash2.p ? stash2_done : nullptr);
-    if (ev && hipStreamWaitEvent(s, ev, 0) != hipSuccess) return NT_EHIP;
-    if (launch() != hipSuccess) return NT_EHIP;
-    if (ev && hipEventRecord(ev, s) != hipSuccess) return NT_EHIP;
-    return NT_OK;
-  }
-
-  // Grow a buffer that enqueue-only device-API calls may still be using: wait
-  // for its last user (the launch that recorded ev) before freeing it.
-  int grow_synced(DevBuf& b, size_t bytes, hipEvent_t ev) {
+  // Grow a buffer that an earlier enqueue-only (device-API) call may still be
+  // using: wait for its last user (the launch that recorded ev) before freeing it.
+  static int grow_synced(DevBuf& b, size_t bytes, hipEvent_t ev) {
     if (bytes <= b.cap) return NT_OK;
     if (b.p && hipEventSynchronize(ev) != hipSuccess) return NT_EHIP;
     return b.ensure(bytes);
   }
-  // the stash / key-grouping scratch pair of slot k (0: d[B_STASH] / d[B_SORT],
-  // 1: stash2 / sort2) for launches of up to m signatures
-  int ensure_stash(int k, uint64_t m) {
-    DevBuf& st = k ? stash2 : d[B_STASH];
-    DevBuf& so = k ? sort2 : d[B_SORT];
-    const hipEvent_t ev = k ? stash2_done : stash_done;
-    const int rc = grow_synced(st, nt::keyset_stash_bytes(m, cus), ev);
-    return rc != NT_OK ? rc : grow_synced(so, nt::keyset_sort_bytes(m), ev);
+
+  // Uncached verify launch on stream s with lane l's [k]A workspace, grown to `slots` workspace
+  // slots (ws_slots x 737 KB is ~1.5 GB at 2,048 slots) and ordered against the workspace's
+  // other users by its event; per_lane as in nt::launch_verify.  A device-API caller (s its own
+  // stream) holds mu.
+  int verify_on(Lane& l, hipStream_t s, int mode, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
+                uint64_t msg_bytes, const uint64_t* off, const uint64_t* len, uint64_t n, uint64_t* out, int per_lane,
+                uint64_t slots) {
+    slots = std::max<uint64_t>(slots, 1);
+    NT_CHK0(grow_synced(l.ws, nt::ws_bytes_per_slot() * slots, l.ws_done));
+    if (hipStreamWaitEvent(s, l.ws_done, 0) != hipSuccess ||
+        nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, l.ws.p, (uint32_t)slots, out, s,
+                          per_lane, xtab()) != hipSuccess ||
+        hipEventRecord(l.ws_done, s) != hipSuccess)
+      return NT_EHIP;
+    return NT_OK;
+  }
+  // ... of host chunk c, on its lane's stream.  Workspace sizes: lane 0's holds ws_slots slots
+  // from the slot's first verify on (verify_tables; ws_bytes_per_slot() is a multiple of 4,096,
+  // so the DevBuf holds exactly that), lane 1's grows to the largest grid a chunk launched
+  // (device-API calls grow either lane's to ws_slots).
+  int verify_host(size_t c, int mode, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint64_t msg_bytes,
+                  const uint64_t* off, const uint64_t* len, uint64_t n, uint64_t* out, int per_lane = 0) {
+    Lane& l = lane[c & 1];
+    return verify_on(l, l.stream, mode, pk, sig, msg, msg_bytes, off, len, n, out, per_lane,
+                     (c & 1) ? nt::verify_grid(n, ws_slots, per_lane) : ws_slots);
   }
 
-  // ws2 holds >= blocks workspace slots; a grown buffer is freed only after its
-  // last user (the kernel that recorded ws2_done) has finished
-  int grow_ws2(uint64_t blocks) {
-    const size_t need = nt::ws_bytes_per_slot() * std::max<uint64_t>(blocks, 1);
-    if (need <= ws2.cap) return NT_OK;
-    if (ws2.p && hipEventSynchronize(ws2_done) != hipSuccess) return NT_EHIP;
-    return ws2.ensure(need);
+  // lane l's key-cache scratch holds launches of up to max_sigs signatures
+  int ensure_scratch(Lane& l, uint64_t max_sigs) {
+    NT_CHK0(grow_synced(l.stash, nt::keyset_stash_bytes(max_sigs, cus), l.stash_done));
+    return grow_synced(l.sort, nt::keyset_sort_bytes(max_sigs), l.stash_done);
   }
-
-  // Device-API verify (nt_dev_ed25519_verify): successive calls alternate between
-  // the two workspaces, each ordered by its own event, so back-to-back batches
-  // issued on two caller streams overlap -- the waves of the next batch fill the
-  // SIMDs the previous batch's last round leaves idle.  Calls on one stream stay
-  // in stream order.  (Caller holds mu.)
-  hipError_t verify_dev(int mode, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint64_t msg_bytes,
-                        const uint64_t* off, const uint64_t* len, uint64_t n, uint64_t* out, hipStream_t s) {
-    if ((dev_calls++ & 1u) == 0) return verify(mode, pk, sig, msg, msg_bytes, off, len, n, out, s);
-    if (grow_ws2(ws_slots) != NT_OK) return hipErrorOutOfMemory;
-    hipError_t e = hipStreamWaitEvent(s, ws2_done, 0);
-    if (e != hipSuccess) return e;
-    e = nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, ws2.p, ws_slots, out, s, 0,
-                          xtab());
-    if (e != hipSuccess) return e;
-    return hipEventRecord(ws2_done, s);
-  }
-
-  // verify launch that shares the workspace: wait for the previous user, then mark
-  hipError_t verify(int mode, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint64_t msg_bytes,
-                    const uint64_t* off, const uint64_t* len, uint64_t n, uint64_t* out, hipStream_t s,
-                    int per_lane = 0) {
-    hipError_t e = hipStreamWaitEvent(s, ws_done, 0);
-    if (e != hipSuccess) return e;
-    e = nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, d_ws, ws_slots, out, s,
-                          per_lane, xtab());
-    if (e != hipSuccess) return e;
-    return hipEventRecord(ws_done, s);
+  // Key-cache launch on stream s with lane l's scratch: launch(nt::KsScratch) enqueues it on s,
+  // after the scratch's previous user (host chunks on the lanes' streams, device-API calls on
+  // any stream) and before its next, like verify_on's workspace.
+  template <class F>
+  int keyset_on(Lane& l, hipStream_t s, uint64_t max_sigs, F&& launch) {
+    NT_CHK0(ensure_scratch(l, max_sigs));
+    if (hipStreamWaitEvent(s, l.stash_done, 0) != hipSuccess ||
+        launch(nt::KsScratch{l.stash.p, l.sort.p}) != hipSuccess || hipEventRecord(l.stash_done, s) != hipSuccess)
+      return NT_EHIP;
+    return NT_OK;
   }
 };
-
 
 }  // namespace ntrt
 
@@ -501,6 +458,12 @@ struct KeyDev {
   int bits = 0;
   uint32_t nkeys = 0;
 };
+// What a key-cache launch on slot dv reads: the first nkeys keys of pd's tables (a key set's,
+// a registry snapshot's or a committee's share on dv's entry) at `bits`-bit digits, and the
+// slot's comb of B (comb_b_for(dv) has run).
+inline nt::KsTabs ks_tabs(const KsTables::PerDev& pd, int bits, uint32_t nkeys, const Device& dv) {
+  return nt::KsTabs{bits, pd.d_meta, pd.d_enc, pd.d_comb, nkeys, dv.d_combB, dv.bbits, dv.cus};
+}
 
 // A published state of the key registry (registry.cpp): the host index of
 // keys 0 .. table.nkeys - 1 and the device tables that hold their combs

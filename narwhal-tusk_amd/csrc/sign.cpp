@@ -30,9 +30,9 @@ int stage_messages(Device& dv, const uint8_t* data, const uint64_t* off, const u
     ho[i - lo] = len[i] ? off[i] - base : 0;
     hl[i - lo] = len[i];
   }
-  if (span) NT_TRY(hipMemcpyAsync(dv.d[B_DATA].p, data + base, span, hipMemcpyHostToDevice, dv.stream));
-  NT_TRY(hipMemcpyAsync(dv.d[B_OFF].p, ho, m * 8, hipMemcpyHostToDevice, dv.stream));
-  NT_TRY(hipMemcpyAsync(dv.d[B_LEN].p, hl, m * 8, hipMemcpyHostToDevice, dv.stream));
+  if (span) NT_TRY(hipMemcpyAsync(dv.d[B_DATA].p, data + base, span, hipMemcpyHostToDevice, dv.lane[0].stream));
+  NT_TRY(hipMemcpyAsync(dv.d[B_OFF].p, ho, m * 8, hipMemcpyHostToDevice, dv.lane[0].stream));
+  NT_TRY(hipMemcpyAsync(dv.d[B_LEN].p, hl, m * 8, hipMemcpyHostToDevice, dv.lane[0].stream));
   *base_out = base;
   *span_out = span;
   return NT_OK;
@@ -73,8 +73,8 @@ int nt_sha512_trunc32(nt_ctx* ctx, const uint8_t* data, const uint64_t* off, con
       return NT_OK;
     }));
     NT_CHK(finish_chunks(dv));
-    NT_TRY(hipMemcpyAsync(out32 + 32 * lo, dv.d[B_OUT].p, m * 32, hipMemcpyDeviceToHost, dv.stream));
-    NT_TRY(hipStreamSynchronize(dv.stream));
+    NT_TRY(hipMemcpyAsync(out32 + 32 * lo, dv.d[B_OUT].p, m * 32, hipMemcpyDeviceToHost, dv.lane[0].stream));
+    NT_TRY(hipStreamSynchronize(dv.lane[0].stream));
     return NT_OK;
   }, sha_latency(n, len));
 }
@@ -101,14 +101,14 @@ int nt_ed25519_sign_batch(nt_ctx* ctx, const uint8_t* seed32, const uint8_t* msg
     NT_CHK(dv.d[B_PK].ensure(m * 32));
     NT_CHK(dv.d[B_SIG].ensure(m * 64));
     NT_CHK(dv.d[B_OUT].ensure(m * 32));
-    NT_TRY(hipMemcpyAsync(dv.d[B_OUT].p, seed32 + 32 * lo, m * 32, hipMemcpyHostToDevice, dv.stream));
+    NT_TRY(hipMemcpyAsync(dv.d[B_OUT].p, seed32 + 32 * lo, m * 32, hipMemcpyHostToDevice, dv.lane[0].stream));
     NT_TRY(nt::launch_sign(dv.d[B_OUT].as<uint8_t>(), d_msg, span, d_off, d_len, m, dv.d_combB, dv.bbits,
                            dv.d[B_PK].as<uint8_t>(), sig64 ? dv.d[B_SIG].as<uint8_t>() : nullptr,
-                           dv.sign_blocks, dv.stream));
-    NT_TRY(hipMemcpyAsync(pk32 + 32 * lo, dv.d[B_PK].p, m * 32, hipMemcpyDeviceToHost, dv.stream));
+                           dv.sign_blocks, dv.lane[0].stream));
+    NT_TRY(hipMemcpyAsync(pk32 + 32 * lo, dv.d[B_PK].p, m * 32, hipMemcpyDeviceToHost, dv.lane[0].stream));
     if (sig64)
-      NT_TRY(hipMemcpyAsync(sig64 + 64 * lo, dv.d[B_SIG].p, m * 64, hipMemcpyDeviceToHost, dv.stream));
-    NT_TRY(hipStreamSynchronize(dv.stream));
+      NT_TRY(hipMemcpyAsync(sig64 + 64 * lo, dv.d[B_SIG].p, m * 64, hipMemcpyDeviceToHost, dv.lane[0].stream));
+    NT_TRY(hipStreamSynchronize(dv.lane[0].stream));
     return NT_OK;
   });
 }

@@ -32,8 +32,8 @@ int verify_items(Device& dv, const Chunks& ch, uint64_t lo, size_t kw, const uin
     return NT_OK;
   }, [&](size_t c) -> int { return launch(c, ch[c].first, ch[c].second, ms); }));
   NT_CHK(finish_chunks(dv));
-  NT_TRY(hipMemcpyAsync(dv.h[B_OUT].p, dv.d[B_OUT].p, words * 8, hipMemcpyDeviceToHost, dv.stream));
-  NT_TRY(hipStreamSynchronize(dv.stream));
+  NT_TRY(hipMemcpyAsync(dv.h[B_OUT].p, dv.d[B_OUT].p, words * 8, hipMemcpyDeviceToHost, dv.lane[0].stream));
+  NT_TRY(hipStreamSynchronize(dv.lane[0].stream));
   words_to_bitmap(out_bitmap + lo / 8, dv.h[B_OUT].as<uint64_t>(), m);
   return NT_OK;
 }
@@ -51,10 +51,10 @@ int verify_strict_gpu(nt_ctx* ctx, const uint8_t* pk32, const uint8_t* sig64, co
     return verify_items(dv, ch, lo, 32, pk32, sig64, msg, off, len, out_bitmap,
                         [&](size_t c, uint64_t a, uint64_t b, const MsgStage& ms) -> int {
       // chunks of at most one round: one signature per lane (half the launch latency)
-      return dv.verify_chunk((int)c, NT_MODE_STRICT, dv.d[B_PK].as<uint8_t>() + 32 * a,
-                             dv.d[B_SIG].as<uint8_t>() + 64 * a, dv.d[B_DATA].as<uint8_t>(), ms.span,
-                             chunk_off(dv, a), chunk_len(dv, a, b), b - a, dv.d[B_OUT].as<uint64_t>() + a / 64,
-                             b - a <= R1 ? 1 : 0);
+      return dv.verify_host(c, NT_MODE_STRICT, dv.d[B_PK].as<uint8_t>() + 32 * a,
+                            dv.d[B_SIG].as<uint8_t>() + 64 * a, dv.d[B_DATA].as<uint8_t>(), ms.span,
+                            chunk_off(dv, a), chunk_len(dv, a, b), b - a, dv.d[B_OUT].as<uint64_t>() + a / 64,
+                            b - a <= R1 ? 1 : 0);
     });
   }, latency_sized(ctx, (n + ctx->devs.size() - 1) / ctx->devs.size(), nt::verify_round_sigs(ctx->devs[0]->cus)));
 }
@@ -64,23 +64,20 @@ int verify_keyset_gpu(nt_ctx* ctx, const KeyDev& kd, int mode, const uint32_t* k
                       const uint8_t* msg, const uint64_t* off, const uint64_t* len, uint64_t n, uint8_t* out_bitmap) {
   return run_sharded(ctx, n, 64, [&](Device& dv, uint64_t lo, uint64_t hi) -> int {
     NT_CHK(comb_b_for(dv));
-    const auto& pd = kd.t->dev[dv.group];
+    const nt::KsTabs tabs = ks_tabs(kd.t->dev[dv.group], kd.bits, kd.nkeys, dv);
     const Chunks ch = nt::plan_chunks(chunk_targets(hi - lo, pipe_round(nt::keyset_round_sigs(dv.cus))));
+    // the scratch of every lane the chunks use, sized for the largest chunk before the pipeline starts
     uint64_t mc = 0;
     for (const auto& c : ch) mc = std::max(mc, c.second - c.first);
-    NT_CHK(dv.ensure_stash(0, mc));
-    if (ch.size() > 1) NT_CHK(dv.ensure_stash(1, mc));
+    for (size_t k = 0; k < std::min<size_t>(ch.size(), 2); ++k) NT_CHK(dv.ensure_scratch(dv.lane[k], mc));
     return verify_items(dv, ch, lo, 4, (const uint8_t*)key_idx, sig64, msg, off, len, out_bitmap,
                         [&](size_t c, uint64_t a, uint64_t b, const MsgStage& ms) -> int {
-      void* st = (c & 1) ? dv.stash2.p : dv.d[B_STASH].p;
-      void* so = (c & 1) ? dv.sort2.p : dv.d[B_SORT].p;
-      hipStream_t s = dv.cstr((int)c);
-      return dv.keyset_launch(s, st, [&] {
-        return nt::launch_verify_keyset(mode, kd.bits, dv.d[B_PK].as<uint32_t>() + a,
+      Lane& l = dv.lane[c & 1];
+      return dv.keyset_on(l, l.stream, mc, [&](nt::KsScratch scratch) {
+        return nt::launch_verify_keyset(mode, tabs, scratch, dv.d[B_PK].as<uint32_t>() + a,
                                         dv.d[B_SIG].as<uint8_t>() + 64 * a, dv.d[B_DATA].as<uint8_t>(), ms.span,
                                         chunk_off(dv, a), chunk_len(dv, a, b), b - a,
-                                        pd.d_meta, pd.d_enc, pd.d_comb, kd.nkeys, dv.d_combB, dv.bbits, st, so,
-                                        dv.d[B_OUT].as<uint64_t>() + a / 64, dv.cus, s);
+                                        dv.d[B_OUT].as<uint64_t>() + a / 64, l.stream);
       });
     });
   }, latency_sized(ctx, (n + ctx->devs.size() - 1) / ctx->devs.size(), nt::keyset_round_sigs(ctx->devs[0]->cus)));

@@ -236,3 +236,47 @@ def test_dev_api_batches_on_two_streams(pair):
             else:
                 assert not got.any()
     ks.close()
+
+
+def test_dev_api_keyset_scratch_grows_between_unsynced_calls():
+    """A lane's key-cache scratch (stash + key-grouping scratch, 5 bytes per
+    signature beside 0.5 MB) grows while earlier enqueue-only calls may still be
+    using it: the corpus tiled x1, x1, x4, x4, x40, x40, x4, x1 through the
+    device API of a fresh context (both lanes start empty), alternating two
+    streams, each call into its own output and no host sync in between.  Every
+    verdict must be the corpus's, and the grow-only scratch must end at what two
+    x40 calls alone leave in another fresh context."""
+    import torch
+    import ntcrypto
+    d = np.load(os.path.join(GOLD, "ed25519_corpus.npz"))
+    dev = torch.device("cuda", 0)
+    tiles = [1, 1, 4, 4, 40, 40, 4, 1]
+    top, per = max(tiles), len(d["pk"])
+    uniq, inv = np.unique(d["pk"], axis=0, return_inverse=True)
+    # a call over r tiles reads the first r * per entries of the x40 inputs
+    sig = torch.from_numpy(np.tile(d["sig"], (top, 1))).to(dev)
+    msg = torch.from_numpy(np.ascontiguousarray(d["msg"])).to(dev)
+    off = torch.from_numpy(np.tile(d["off"], top).astype(np.int64)).to(dev)
+    ln = torch.from_numpy(np.tile(d["len"], top).astype(np.int64)).to(dev)
+    kidx = torch.from_numpy(np.tile(inv.ravel().astype(np.uint32), top).view(np.int32)).to(dev)
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+
+    def run(reps):
+        be = ntcrypto.Backend(devices=[0])
+        ks = be.keyset(uniq)
+        outs = [torch.zeros((r * per + 63) // 64, dtype=torch.int64, device=dev) for r in reps]
+        torch.cuda.synchronize(dev)
+        for i, r in enumerate(reps):
+            ks.dev_verify(0, streams[i % 2].cuda_stream, ntcrypto.NT_MODE_STRICT, kidx.data_ptr(), sig.data_ptr(),
+                          msg.data_ptr(), nbytes(msg), off.data_ptr(), ln.data_ptr(), r * per, outs[i].data_ptr())
+        torch.cuda.synchronize(dev)
+        stash = be.memory_info()["stash_bytes"]
+        ks.close()
+        be.close()
+        return stash, [np.unpackbits(o.cpu().numpy().view(np.uint8), bitorder="little")[:r * per].astype(bool)
+                       for o, r in zip(outs, reps)]
+
+    stash, got = run(tiles)
+    for r, g in zip(tiles, got):
+        assert np.array_equal(g, np.tile(d["strict"], r).astype(bool)), r
+    assert stash == run([top, top])[0] > 0
