@@ -280,6 +280,65 @@ int nt_primary_messages_ingest(nt_ctx *ctx, const nt_committee *cm, const uint8_
                                const uint64_t *len, uint64_t n, uint64_t gc_round, const uint8_t *cur_id32,
                                uint64_t cur_round, const uint8_t *cur_author32, uint8_t *out_code);
 
+/* The receipt of one message: what the device knew about it when it decided
+ * its code -- the layout the parser walked (csrc/msg_plan.hpp), the committee
+ * indices of its key strings, the id it claims and the digest the chunk's
+ * SHA-512 launch computed.  A caller processes an accepted message from its
+ * own wire bytes in place: no bincode decoder, no base64, no hashing.
+ * Offsets are relative to the message's first byte (data + off[i]); the
+ * parser's caps (2^20 payload entries, 2^20 parents or request digests, 1024
+ * votes) keep every one of them below 2^27, so 32 bits hold them.  Each offset
+ * plus the extent its count gives lies inside the message (len[i]).
+ *   header / certificate  author = origin = the author's committee index;
+ *                         off_payload = 72 when np > 0; off_parents, off_id and
+ *                         off_sig as walked; off_votes and nv for a certificate
+ *   vote                  author = the voter, origin = the header author it
+ *                         names; off_id = 4, off_sig = 148; id = the header id
+ *                         it names, digest = Vote::digest
+ *   request               author = origin = the requestor; nq digests at
+ *                         off_parents = 12; everything else zero
+ * code == NT_DAG_HOST: kind = 0xff and every other byte zero -- the caller
+ * decodes that message itself.  For every other message all fields are defined
+ * whatever the code (TooOld and InvalidSignature included: the SHA-512 launch
+ * covers every parsed message).  The natural C layout has no padding. */
+#define NT_RECEIPT_KIND_HOST 0xff
+#define NT_RECEIPT_GENESIS 1u /* flags bit 0 */
+typedef struct nt_msg_receipt {
+  uint8_t code;         /* the byte out_code[i] gets */
+  uint8_t kind;         /* 0 header, 1 vote, 2 certificate, 3 request; 0xff = NT_DAG_HOST */
+  uint16_t flags;       /* bit 0: accepted as a committee member's genesis certificate */
+  uint32_t author;      /* committee index (the key's position in the nt_keyset) */
+  uint32_t origin;      /* a vote's origin; otherwise = author */
+  uint32_t np, nq, nv;  /* payload entries, parents (a request: its digests), certificate votes */
+  uint64_t round;       /* header / certificate / vote round; 0 for a request */
+  uint32_t off_payload; /* np x (digest 32, worker u32 LE); 0 when there is none */
+  uint32_t off_parents; /* nq x digest 32, ascending (a request's digests: in wire order) */
+  uint32_t off_id;      /* the 32-byte id in the message; 0 for a request */
+  uint32_t off_sig;     /* the message's own 64-byte signature; 0 for a request */
+  uint32_t off_votes;   /* nv x (u64 44, key text 44, signature 64); 0 unless a certificate */
+  uint8_t id[32];       /* the bytes at off_id; zero for a request */
+  uint8_t digest[32];   /* header: SHA-512[..32] of its preimage (equals id unless the code is
+                           InvalidHeaderId or an earlier check failed first); certificate:
+                           Certificate::digest; vote: Vote::digest; request: zero */
+  uint8_t reserved[12]; /* zero */
+} nt_msg_receipt;
+#if defined(__cplusplus)
+static_assert(sizeof(nt_msg_receipt) == 128, "nt_msg_receipt is 128 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nt_msg_receipt) == 128, "nt_msg_receipt is 128 bytes");
+#else /* C99 has no static assertion: an array type of size -1 does not compile */
+typedef char nt_msg_receipt_is_128_bytes[sizeof(nt_msg_receipt) == 128 ? 1 : -1];
+#endif
+/* nt_primary_messages_ingest plus one receipt per message: out_code is byte
+ * for byte what that call returns for the same arguments, and all n x 128
+ * bytes of out_receipt are written (NULL with n > 0: NT_EINVAL).  Same
+ * chunking, streams, sharding and pinned-input rule; one more short kernel per
+ * chunk and 128 bytes per message copied back beside the codes. */
+int nt_primary_messages_ingest_receipts(nt_ctx *ctx, const nt_committee *cm, const uint8_t *data,
+                                        const uint64_t *off, const uint64_t *len, uint64_t n, uint64_t gc_round,
+                                        const uint8_t *cur_id32, uint64_t cur_round, const uint8_t *cur_author32,
+                                        uint8_t *out_code, nt_msg_receipt *out_receipt);
+
 /* ---- small-call path (SURVEY.md H3, §8(b) "CPU-fallback threshold") ------
  * The reference calls verify once per header / vote, verify_batch once per
  * certificate (primary/src/core.rs:349-411) and hashes one ~508 KB batch per
@@ -341,6 +400,11 @@ void nt_host_free(void *p);
  * digest and adds 1 to *d_bad (a device counter the caller zeroes; NULL = not
  * counted).  So an offset read before its producer wrote it (round 4's fault
  * r04e: a wild offset from a cross-stream race) cannot fault the card.
+ * The wire-ingestion calls above (nt_certificates_ingest,
+ * nt_primary_messages_ingest, nt_primary_messages_ingest_receipts) follow the
+ * same rule for untrusted bytes: their parser bounds every count and offset by
+ * the message length before it is used (csrc/msg_plan.hpp), and the offsets a
+ * receipt reports are those bounded ones.
  *
  * The uncached verify kernel (nt_dev_ed25519_verify, the host entry points'
  * chunks) keeps the decompressed x of the public keys it has seen in a table

@@ -1,7 +1,8 @@
 // ingest_gpu.cpp -- C ABI of the message ingestion from wire bytes
 // (include/ntcrypto.h: nt_committee_*, nt_certificates_ingest,
-// nt_primary_messages_ingest; kernels in k_ingest.hip).  The two entry points
-// share everything below; they differ in the kinds the kernels decide.
+// nt_primary_messages_ingest, nt_primary_messages_ingest_receipts; kernels in
+// k_ingest.hip).  The entry points share everything below; they differ in the
+// kinds the kernels decide and in whether a receipt per message comes back.
 //
 // Per device shard the messages are cut into chunks that alternate between
 // the slot's two compute streams.  A chunk is two halves:
@@ -11,7 +12,8 @@
 //   back:  (needs the vote total V to size the launch) scatter into the launch
 //          buffers, one SHA-512 launch (header ids + certificate digests), one
 //          NT_MODE_MIXED key-cache launch over n + V signatures, group AND,
-//          verdicts, codes back to pinned host memory.
+//          verdicts, codes back to pinned host memory; with receipts, one more
+//          kernel (k_msg_receipt) and 128 bytes per message after the codes.
 // The host issues front(c) before waiting for front(c - 1)'s totals and
 // issuing back(c - 1), so chunk c's PCIe copy and parse run under chunk
 // c - 1's signature launch on the other stream.
@@ -69,6 +71,7 @@ constexpr uint64_t kSlack = 64;  // readable bytes before / after the wire bytes
 
 struct Side {  // device buffers of one chunk parity, grow-only
   DevBuf wire, moff, mlen, round, u32s, scans, mbase, keys, sigs, smsg, sha, grp, words, code;
+  DevBuf rec;  // the chunk's receipts, only in calls that ask for them
   HostBuf tot;
   hipEvent_t ev = nullptr;  // the chunk's front half is done, its totals in `tot`
   ~Side() {
@@ -78,7 +81,7 @@ struct Side {  // device buffers of one chunk parity, grow-only
 
 struct IngestState {  // goes with its slot (~Device has set the device)
   Side side[2];
-  HostBuf hoff, hlen, hcode;
+  HostBuf hoff, hlen, hcode, hrec;
 };
 
 // grow a buffer the stream's earlier work may still use: wait for it first
@@ -185,16 +188,19 @@ void nt_committee_free(nt_committee* cm) { delete cm; }
 
 namespace {
 
-// what one call decides: the kinds, the GC round and the header being voted on
+// what one call decides: the kinds, the GC round and the header being voted on;
+// and where its receipts go (null: none, and nothing is launched or copied for them)
 struct IngestRules {
   uint32_t kinds = nt::kMsgKindsCert;
   uint64_t gc_round = 0;
   nt::MsgCurrent cur{};
+  nt_msg_receipt* receipts = nullptr;
 };
 
 // front half of chunk ch on stream s (see the file comment)
 int ingest_front(Device& dv, IngestState& S, Side& sd, Chunk& ch, const nt_committee::PerDev& pd,
-                 const uint8_t* data, const uint64_t* off, const uint64_t* len, uint32_t kinds, hipStream_t s) {
+                 const uint8_t* data, const uint64_t* off, const uint64_t* len, const IngestRules& rules,
+                 hipStream_t s) {
   const uint64_t m = ch.b - ch.a;
   uint64_t* ho = S.hoff.as<uint64_t>() + ch.a;
   uint64_t* hl = S.hlen.as<uint64_t>() + ch.a;
@@ -224,6 +230,7 @@ int ingest_front(Device& dv, IngestState& S, Side& sd, Chunk& ch, const nt_commi
   NT_CHK0(grow(sd.sha, m * 32, s));
   NT_CHK0(grow(sd.grp, m * 8 + (m / 64 + 2) * 8, s));
   NT_CHK0(grow(sd.code, m, s));
+  if (rules.receipts) NT_CHK0(grow(sd.rec, m * sizeof(nt_msg_receipt), s));  // reused like `code`
   NT_CHK0(sd.tot.ensure(16));
   uint8_t* wire = sd.wire.as<uint8_t>();
   if (ch.span) NT_TRY(hipMemcpyAsync(wire + kSlack, data + ch.base, ch.span, hipMemcpyHostToDevice, s));
@@ -235,7 +242,7 @@ int ingest_front(Device& dv, IngestState& S, Side& sd, Chunk& ch, const nt_commi
   b.moff = sd.moff.as<uint64_t>();
   b.mlen = sd.mlen.as<uint64_t>();
   b.n = m;
-  b.kinds = kinds;
+  b.kinds = rules.kinds;
   b.round = sd.round.as<uint64_t>();
   uint32_t* u = sd.u32s.as<uint32_t>();
   b.author = u;
@@ -254,6 +261,7 @@ int ingest_front(Device& dv, IngestState& S, Side& sd, Chunk& ch, const nt_commi
   b.gfirst = sd.grp.as<uint64_t>();
   b.grp_words = b.gfirst + m;
   b.code = sd.code.as<uint8_t>();
+  b.rec = rules.receipts ? sd.rec.as<uint4>() : nullptr;
   NT_TRY(nt::launch_cert_parse(pd.c, b, s));
   NT_TRY(nt::launch_cert_scan(b, s));
   // the totals: vbase[m], pbase[m]
@@ -298,6 +306,11 @@ int ingest_back(Device& dv, IngestState& S, Side& sd, Lane& lane, Chunk& ch, con
   }));
   NT_TRY(nt::launch_cert_verdict(pd.c, b, rules.gc_round, rules.cur, s));
   NT_TRY(hipMemcpyAsync(S.hcode.as<uint8_t>() + ch.a, b.code, m, hipMemcpyDeviceToHost, s));
+  if (rules.receipts) {
+    NT_TRY(nt::launch_msg_receipt(pd.c, b, rules.gc_round, s));
+    NT_TRY(hipMemcpyAsync(S.hrec.as<nt_msg_receipt>() + ch.a, b.rec, m * sizeof(nt_msg_receipt),
+                          hipMemcpyDeviceToHost, s));
+  }
   return NT_OK;
 }
 
@@ -317,6 +330,7 @@ int ingest_shard(Device& dv, const nt_committee& cm, const uint8_t* data, const 
   NT_CHK0(S.hoff.ensure(n * 8));
   NT_CHK0(S.hlen.ensure(n * 8));
   NT_CHK0(S.hcode.ensure(n));
+  if (rules.receipts) NT_CHK0(S.hrec.ensure(n * sizeof(nt_msg_receipt)));
   const nt_committee::PerDev& pd = cm.dev[dv.group];
   const uint64_t C = chunk_msgs();
   std::vector<Chunk> ch;
@@ -330,11 +344,12 @@ int ingest_shard(Device& dv, const nt_committee& cm, const uint8_t* data, const 
   const uint64_t* o = off + lo;
   const uint64_t* l = len + lo;
   for (size_t k = 0; k <= ch.size(); ++k) {
-    if (k < ch.size()) NT_CHK0(ingest_front(dv, S, S.side[k & 1], ch[k], pd, d, o, l, rules.kinds, dv.cstr((int)k)));
+    if (k < ch.size()) NT_CHK0(ingest_front(dv, S, S.side[k & 1], ch[k], pd, d, o, l, rules, dv.cstr((int)k)));
     if (k >= 1) NT_CHK0(ingest_back(dv, S, S.side[(k - 1) & 1], dv.lane[(k - 1) & 1], ch[k - 1], cm, pd, rules));
   }
   for (Lane& l : dv.lane) NT_TRY(hipStreamSynchronize(l.stream));
   std::memcpy(out + lo, S.hcode.p, n);
+  if (rules.receipts) std::memcpy(rules.receipts + lo, S.hrec.p, n * sizeof(nt_msg_receipt));
   return NT_OK;
 }
 
@@ -346,6 +361,20 @@ int ingest_call(nt_ctx* ctx, const nt_committee* cm, const uint8_t* data, const 
   return run_sharded(ctx, n, 1, [&](Device& dv, uint64_t lo, uint64_t hi) {
     return ingest_shard(dv, *cm, data, off, len, lo, hi, rules, out_code);
   });
+}
+
+// the whole drain's rules (nt_primary_messages_ingest*)
+IngestRules message_rules(uint64_t gc_round, const uint8_t* cur_id32, uint64_t cur_round, const uint8_t* cur_author32,
+                          nt_msg_receipt* receipts) {
+  IngestRules rules;
+  rules.kinds = nt::kMsgKindsAll;
+  rules.gc_round = gc_round;
+  rules.cur.round = cur_round;  // a null id / author: 32 zero bytes (Header::default())
+  if (cur_id32) std::memcpy(&rules.cur.w[0], cur_id32, 32);
+  std::memcpy(&rules.cur.w[8], &cur_round, 8);
+  if (cur_author32) std::memcpy(&rules.cur.w[10], cur_author32, 32);
+  rules.receipts = receipts;
+  return rules;
 }
 
 }  // namespace
@@ -362,14 +391,17 @@ int nt_certificates_ingest(nt_ctx* ctx, const nt_committee* cm, const uint8_t* d
 int nt_primary_messages_ingest(nt_ctx* ctx, const nt_committee* cm, const uint8_t* data, const uint64_t* off,
                                const uint64_t* len, uint64_t n, uint64_t gc_round, const uint8_t* cur_id32,
                                uint64_t cur_round, const uint8_t* cur_author32, uint8_t* out_code) {
-  IngestRules rules;
-  rules.kinds = nt::kMsgKindsAll;
-  rules.gc_round = gc_round;
-  rules.cur.round = cur_round;  // a null id / author: 32 zero bytes (Header::default())
-  if (cur_id32) std::memcpy(&rules.cur.w[0], cur_id32, 32);
-  std::memcpy(&rules.cur.w[8], &cur_round, 8);
-  if (cur_author32) std::memcpy(&rules.cur.w[10], cur_author32, 32);
-  return ingest_call(ctx, cm, data, off, len, n, rules, out_code);
+  return ingest_call(ctx, cm, data, off, len, n, message_rules(gc_round, cur_id32, cur_round, cur_author32, nullptr),
+                     out_code);
+}
+
+int nt_primary_messages_ingest_receipts(nt_ctx* ctx, const nt_committee* cm, const uint8_t* data,
+                                        const uint64_t* off, const uint64_t* len, uint64_t n, uint64_t gc_round,
+                                        const uint8_t* cur_id32, uint64_t cur_round, const uint8_t* cur_author32,
+                                        uint8_t* out_code, nt_msg_receipt* out_receipt) {
+  if (n && !out_receipt) return NT_EINVAL;
+  return ingest_call(ctx, cm, data, off, len, n,
+                     message_rules(gc_round, cur_id32, cur_round, cur_author32, out_receipt), out_code);
 }
 
 }  // extern "C"

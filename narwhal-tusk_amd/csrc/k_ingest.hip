@@ -20,11 +20,14 @@
 //                   unknown error and the stake they carry
 //   k_cert_verdict  one thread per message: the DagError of the first failing
 //                   check, in the reference order
+//   k_msg_receipt   one thread per message, only when the call asked for
+//                   receipts: the 128-byte record of msg_receipt.hpp
 // Message bytes are read with aligned dword loads joined by v_alignbyte (the
 // wire buffer keeps 64 bytes of slack on both sides), so messages may start
 // at any byte.
 #include "kernels_common.hpp"
 #include "msg_plan.hpp"
+#include "msg_receipt.hpp"
 
 namespace nt {
 
@@ -397,6 +400,41 @@ __global__ __launch_bounds__(kBlock) void k_cert_verdict(CertCommittee c, CertBu
   b.code[i] = (uint8_t)code;
 }
 
+// The receipt of message i (msg_receipt.hpp; launched only when a call asked
+// for receipts): one thread per message, the record assembled in registers and
+// written as eight 16-byte stores that fill the thread's own 128-byte line.
+// The plan is the walk k_cert_parse made (same bytes, same bounds: nothing is
+// read outside the message but the id, inside it by the walk's own check); a
+// vote's origin index is looked up again, as k_cert_scatter does.  A message
+// the host decides never has its bytes read here.
+__global__ __launch_bounds__(kBlock) void k_msg_receipt(CertCommittee c, CertBufs b, uint64_t gc_round) {
+  aux_priority();
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= b.n) return;
+  const uint32_t fl = b.flags[i], code = b.code[i];
+  uint32_t w[kReceiptWords];
+  if ((fl & kCertHost) || code == kReceiptHostCode) {
+    msg_receipt_words(MsgPlan{}, kReceiptHostCode, 0, 0, gc_round, nullptr, nullptr, w);
+  } else {
+    const uint8_t* p = b.wire + b.moff[i];
+    const MsgPlan m = msg_walk(WireLd{p}, b.mlen[i], b.kinds);
+    const uint32_t author = b.author[i];
+    uint32_t origin = author, id[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dig[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (m.kind == kMsgVote) origin = key_lookup(c, p + m.key0);  // found (k_cert_parse)
+    if (m.kind != kMsgRequest && m.kind != kMsgHost) {
+      ldwords<8>(p + m.off_id, id);
+      const uint4* d = (const uint4*)(b.mbase + msg_receipt_digest_off(m.kind, b.n, i));
+      const uint4 lo = d[0], hi = d[1];
+      dig[0] = lo.x; dig[1] = lo.y; dig[2] = lo.z; dig[3] = lo.w;
+      dig[4] = hi.x; dig[5] = hi.y; dig[6] = hi.z; dig[7] = hi.w;
+    }
+    msg_receipt_words(m, code, author, origin, gc_round, id, dig, w);
+  }
+  uint4* out = b.rec + 8 * i;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) out[r] = make_uint4(w[4 * r], w[4 * r + 1], w[4 * r + 2], w[4 * r + 3]);
+}
+
 hipError_t launch_cert_parse(const CertCommittee& c, const CertBufs& b, hipStream_t s) {
   if (b.n == 0) return hipSuccess;
   const uint64_t blocks = (b.n + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -419,6 +457,13 @@ hipError_t launch_cert_verdict(const CertCommittee& c, const CertBufs& b, uint64
   if (b.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_cert_verdict, dim3((uint32_t)((b.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, b,
                      gc_round, cur);
+  return hipGetLastError();
+}
+hipError_t launch_msg_receipt(const CertCommittee& c, const CertBufs& b, uint64_t gc_round, hipStream_t s) {
+  if (b.n == 0) return hipSuccess;
+  if (!b.rec) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_msg_receipt, dim3((uint32_t)((b.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, b,
+                     gc_round);
   return hipGetLastError();
 }
 

@@ -138,6 +138,7 @@ struct CertBufs {
   const uint64_t* sig_words;  // verdict words of the key-cache launch
   const uint64_t* grp_words;  // group AND words
   uint8_t* code;              // per message: primary::DagError, 0xff = host decoder
+  uint4* rec;                 // per message: the 128-byte receipt (msg_receipt.hpp); null = none asked for
 };
 hipError_t launch_cert_parse(const CertCommittee& c, const CertBufs& b, hipStream_t s);
 hipError_t launch_cert_scan(const CertBufs& b, hipStream_t s);
@@ -150,5 +151,7 @@ struct MsgCurrent {
 };
 hipError_t launch_cert_verdict(const CertCommittee& c, const CertBufs& b, uint64_t gc_round, const MsgCurrent& cur,
                                hipStream_t s);
+// after launch_cert_verdict on the same stream; needs b.rec
+hipError_t launch_msg_receipt(const CertCommittee& c, const CertBufs& b, uint64_t gc_round, hipStream_t s);
 
 }  // namespace nt

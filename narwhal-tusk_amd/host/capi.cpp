@@ -108,6 +108,22 @@ int ntn_core_ingest(void* p, const uint8_t* data, const uint64_t* off, const uin
   }
 }
 
+// Core::ingest_device_receipts: ingest mode 3's codes plus n 128-byte receipts
+// (nt_msg_receipt) in out_receipts; *host_decided = messages left to the host decoder.
+int ntn_core_ingest_receipts(void* p, const uint8_t* data, const uint64_t* off, const uint64_t* len, uint64_t n,
+                             int threads, int32_t* out_codes, uint8_t* out_receipts, uint64_t* host_decided) {
+  try {
+    size_t host = 0;
+    const auto r = ((CoreHandle*)p)->core.ingest_device_receipts(data, off, len, (size_t)n,
+                                                                 (nt_msg_receipt*)out_receipts, threads, &host);
+    for (uint64_t i = 0; i < n; ++i) out_codes[i] = (int32_t)r[i];
+    if (host_decided) *host_decided = host;
+    return 0;
+  } catch (const std::exception&) {
+    return -2;
+  }
+}
+
 // Core::ingest_pipelined: chunks of `chunk` messages, two in flight.
 int ntn_core_ingest_pipelined(void* p, const uint8_t* data, const uint64_t* off, const uint64_t* len, uint64_t n,
                               int threads, uint64_t chunk, int32_t* out_codes) {

@@ -670,6 +670,19 @@ std::vector<DagError> Core::ingest_device_all(const uint8_t* data, const uint64_
   return finish_on_host(*this, code, data, off, len, n, threads, host_decided);
 }
 
+std::vector<DagError> Core::ingest_device_receipts(const uint8_t* data, const uint64_t* off, const uint64_t* len,
+                                                   size_t n, nt_msg_receipt* receipts, int threads,
+                                                   size_t* host_decided) const {
+  nt_ctx* ctx = crypto::Backend::global().ctx();
+  nt_committee* dc = device_committee(*this, ctx);
+  std::vector<uint8_t> code(std::max<size_t>(n, 1));
+  if (n) check(nt_primary_messages_ingest_receipts(ctx, dc, data, off, len, n, gc_round,
+                                                   current_header.id.bytes.data(), current_header.round,
+                                                   current_header.author.bytes.data(), code.data(), receipts),
+               "nt_primary_messages_ingest_receipts");
+  return finish_on_host(*this, code, data, off, len, n, threads, host_decided);
+}
+
 std::vector<DagError> Core::ingest_pipelined(const uint8_t* data, const uint64_t* off, const uint64_t* len,
                                              size_t n, int threads, size_t chunk) const {
   if (chunk == 0 || chunk >= n) return ingest_soa(data, off, len, n, threads);

@@ -28,6 +28,8 @@
 
 #include "crypto.hpp"
 
+struct nt_msg_receipt;  // include/ntcrypto.h
+
 namespace primary {
 
 using crypto::Digest;
@@ -167,6 +169,17 @@ struct Core {
   // bytes, keys outside the committee) go through ingest_soa.  Same verdicts.
   std::vector<DagError> ingest_device_all(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
                                           int threads = 1, size_t* host_decided = nullptr) const;
+  // ingest_device_receipts: ingest_device_all plus the device's receipt of every
+  // message (nt_primary_messages_ingest_receipts; ntcrypto.h nt_msg_receipt):
+  // `receipts` (n records, the caller's) is written whole.  A message the device
+  // left to the host gets its DagError from ingest_soa, as above, and keeps
+  // kind = 0xff with a zeroed record (its code byte stays NT_DAG_HOST): the
+  // caller decodes that one itself.
+  // author / origin count the authorities in committee->authorities' order (the
+  // map's: ascending key bytes), the order of the key cache.
+  std::vector<DagError> ingest_device_receipts(const uint8_t* data, const uint64_t* off, const uint64_t* len,
+                                               size_t n, nt_msg_receipt* receipts, int threads = 1,
+                                               size_t* host_decided = nullptr) const;
   // the batch in chunks of `chunk` messages, two chunks in flight on two
   // workspaces: one chunk's host decode and checks overlap the other's GPU
   // launches.  Same verdicts as ingest (messages are independent).

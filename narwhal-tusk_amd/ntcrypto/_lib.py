@@ -37,8 +37,19 @@ EXPORTED = [
     "nt_committee_create", "nt_committee_free", "nt_certificates_ingest", "nt_small_call_model",
     "nt_set_hbm_budget", "nt_memory_info", "nt_dev_stream", "nt_set_key_cache", "nt_key_cache_add",
     "nt_key_cache_sync", "nt_key_cache_info", "nt_dev_clock_probe", "nt_dev_ed25519_verify_keyset_groups",
-    "nt_primary_messages_ingest",
+    "nt_primary_messages_ingest", "nt_primary_messages_ingest_receipts",
 ]
+# nt_msg_receipt (include/ntcrypto.h): one 128-byte record per ingested message
+RECEIPT_DTYPE = np.dtype({
+    "names": ["code", "kind", "flags", "author", "origin", "np", "nq", "nv", "round", "off_payload", "off_parents",
+              "off_id", "off_sig", "off_votes", "id", "digest", "reserved"],
+    "formats": ["u1", "u1", "<u2", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", "<u4", "<u4", "<u4", "<u4", "<u4",
+                ("u1", 32), ("u1", 32), ("u1", 12)],
+    "offsets": [0, 1, 2, 4, 8, 12, 16, 20, 24, 32, 36, 40, 44, 48, 52, 84, 116],
+    "itemsize": 128,
+})
+RECEIPT_KIND_HOST = 0xFF
+RECEIPT_GENESIS = 1           # flags bit 0
 KEY_CACHE_INFO_KEYS = ("keys", "max_keys", "comb_bits", "bytes_per_device", "hits", "misses", "admitted", "refused",
                        "pending", "error", "alloc_us", "build_us")
 MEMORY_INFO_KEYS = ("comb_b_bits", "comb_b_bytes", "key_comb_bytes", "workspace_bytes", "stash_bytes",
@@ -104,6 +115,9 @@ def load_library(path=None):
     lib.nt_certificates_ingest.argtypes = [_vp, _vp, _u8p, _u64p, _u64p, _u64, _u64, _u8p]
     if hasattr(lib, "nt_primary_messages_ingest"):  # absent from older A/B builds (NTCRYPTO_LIB)
         lib.nt_primary_messages_ingest.argtypes = [_vp, _vp, _u8p, _u64p, _u64p, _u64, _u64, _u8p, _u64, _u8p, _u8p]
+    if hasattr(lib, "nt_primary_messages_ingest_receipts"):  # absent from older A/B builds (NTCRYPTO_LIB)
+        lib.nt_primary_messages_ingest_receipts.argtypes = [_vp, _vp, _u8p, _u64p, _u64p, _u64, _u64, _u8p, _u64, _u8p,
+                                                            _u8p, _vp]
     if hasattr(lib, "nt_memory_info"):  # absent from round-3 A/B builds (NTCRYPTO_LIB)
         lib.nt_set_hbm_budget.argtypes = [_vp, ctypes.c_uint64]
         lib.nt_memory_info.argtypes = [_vp, ctypes.c_int, _u64p]
@@ -502,22 +516,34 @@ class Committee:
                                                   int(gc_round), _p(out)), "nt_certificates_ingest")
         return out[:n]
 
-    def ingest_messages(self, messages, gc_round=0, cur_id=None, cur_round=0, cur_author=None):
+    def ingest_messages(self, messages, gc_round=0, cur_id=None, cur_round=0, cur_author=None, receipts=False):
         """The whole drain on the device (nt_primary_messages_ingest): headers, votes,
         certificates and requests.  cur_id / cur_round / cur_author: the header being
         voted on (32-byte id, round, the author's raw 32-byte key; None = zero bytes).
-        Returns the raw codes, NT_DAG_HOST (0xff) included."""
+        Returns the raw codes, NT_DAG_HOST (0xff) included.  receipts=True
+        (nt_primary_messages_ingest_receipts): (codes, receipts), the second a
+        RECEIPT_DTYPE array with one record per message; an array passed as
+        `receipts` (n records, C-contiguous) is filled in place and returned."""
         n = len(messages)
         data, off, ln, out = self._packed(messages)
         cid = np.frombuffer(bytes(cur_id), np.uint8) if cur_id is not None else None
         cau = np.frombuffer(bytes(cur_author), np.uint8) if cur_author is not None else None
         if (cid is not None and len(cid) != 32) or (cau is not None and len(cau) != 32):
             raise ValueError("cur_id and cur_author are 32 bytes each")
-        _check(self.be.lib.nt_primary_messages_ingest(
-            self.be.ctx, self.h, _p(data), _p(off, _u64p), _p(ln, _u64p), n, int(gc_round),
-            _p(cid) if cid is not None else None, int(cur_round), _p(cau) if cau is not None else None, _p(out)),
-            "nt_primary_messages_ingest")
-        return out[:n]
+        args = (self.be.ctx, self.h, _p(data), _p(off, _u64p), _p(ln, _u64p), n, int(gc_round),
+                _p(cid) if cid is not None else None, int(cur_round), _p(cau) if cau is not None else None, _p(out))
+        if receipts is False or receipts is None:
+            _check(self.be.lib.nt_primary_messages_ingest(*args), "nt_primary_messages_ingest")
+            return out[:n]
+        if receipts is True:
+            rec = np.zeros(max(n, 1), RECEIPT_DTYPE)
+        else:
+            rec = receipts
+            if rec.dtype != RECEIPT_DTYPE or rec.ndim != 1 or len(rec) != n or not rec.flags.c_contiguous:
+                raise ValueError("receipts: a C-contiguous RECEIPT_DTYPE array of one record per message")
+        _check(self.be.lib.nt_primary_messages_ingest_receipts(*args, rec.ctypes.data_as(_vp) if n else None),
+               "nt_primary_messages_ingest_receipts")
+        return out[:n], rec[:n]
 
     def close(self):
         if getattr(self, "h", None):

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._lib import PKG_ROOT, NtError
+from ._lib import PKG_ROOT, RECEIPT_DTYPE, NtError
 
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libntnarwhal.so")
 DAG_ERRORS = ["Ok", "InvalidSignature", "InvalidHeaderId", "MalformedHeader", "UnknownAuthority",
@@ -44,6 +44,9 @@ def load():
         lib.ntn_core_ingest.argtypes = [ctypes.c_void_p, _u8p, _u64p, _u64p, ctypes.c_uint64, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), ctypes.c_int]
         lib.ntn_core_ingest.restype = ctypes.c_int
+        lib.ntn_core_ingest_receipts.argtypes = [ctypes.c_void_p, _u8p, _u64p, _u64p, ctypes.c_uint64, ctypes.c_int,
+                                                 ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, _u64p]
+        lib.ntn_core_ingest_receipts.restype = ctypes.c_int
         lib.ntn_core_ingest_pipelined.argtypes = [ctypes.c_void_p, _u8p, _u64p, _u64p, ctypes.c_uint64, ctypes.c_int,
                                                   ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32)]
         lib.ntn_core_ingest_pipelined.restype = ctypes.c_int
@@ -115,7 +118,7 @@ class Core:
         if not self._h:
             raise NtError("ntn_core_new failed (no gfx950 device, or a bad current header)")
 
-    def ingest(self, data, off, ln, threads=8, general=False, device=False):
+    def ingest(self, data, off, ln, threads=8, general=False, device=False, receipts=False):
         """DagError codes for n packed wire messages; also returns the host decode
         seconds.  general=True: the object-model decoder (cross-check path).
         device=True: Core::ingest_device -- certificates parsed and checked on the
@@ -123,13 +126,29 @@ class Core:
         the second value is then the count of messages the host decided.
         device="all": Core::ingest_device_all -- headers, votes and requests are
         decided on the GPU too (nt_primary_messages_ingest); only irregular bytes
-        are left to the host, counted in the second value."""
+        are left to the host, counted in the second value.
+        receipts=True (with device="all"): Core::ingest_device_receipts -- a third
+        value, the RECEIPT_DTYPE record of every message (ntcrypto.h
+        nt_msg_receipt); a message the host decided keeps kind 0xff and a zeroed
+        record."""
         n = len(off)
         codes = np.zeros(max(n, 1), np.int32)
         dec = ctypes.c_double(0)
         data = np.ascontiguousarray(data, np.uint8)
         off = np.ascontiguousarray(off, np.uint64)
         ln = np.ascontiguousarray(ln, np.uint64)
+        if receipts:
+            if device != "all":
+                raise ValueError('receipts=True needs device="all"')
+            rec = np.zeros(max(n, 1), RECEIPT_DTYPE)
+            host = ctypes.c_uint64(0)
+            rc = load().ntn_core_ingest_receipts(self._h, data.ctypes.data_as(_u8p), off.ctypes.data_as(_u64p),
+                                                 ln.ctypes.data_as(_u64p), n, threads,
+                                                 codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                 rec.ctypes.data_as(ctypes.c_void_p), ctypes.byref(host))
+            if rc != 0:
+                raise NtError("ntn_core_ingest_receipts: backend failure")
+            return codes[:n], int(host.value), rec[:n]
         rc = load().ntn_core_ingest(self._h, data.ctypes.data_as(_u8p), off.ctypes.data_as(_u64p),
                                     ln.ctypes.data_as(_u64p), n, threads,
                                     codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(dec),
