@@ -339,6 +339,82 @@ int nt_primary_messages_ingest_receipts(nt_ctx *ctx, const nt_committee *cm, con
                                         const uint8_t *cur_id32, uint64_t cur_round, const uint8_t *cur_author32,
                                         uint8_t *out_code, nt_msg_receipt *out_receipt);
 
+/* ---- the worker's message ingestion on the device -----------------------
+ * What a worker does with every message from another worker
+ * (worker/src/worker.rs:270-292, worker/src/processor.rs:36-48): bincode-
+ * decode the whole WorkerMessage to learn its variant, hand the serialized
+ * bytes of a Batch to the Processor, hash them (SHA-512[..32]) and emit
+ * OthersBatch(digest, id).  This call takes the drain as it arrived and
+ * returns a code and a receipt per message, batches and requests alike; the
+ * receipt of a batch carries the Processor's digest.  It needs no key set and
+ * no committee, and builds no table (a worker verifies nothing).
+ *
+ *   Batch         u32 0 | u64 ntx | ntx x (u64 len_k | len_k bytes)
+ *   BatchRequest  u32 1 | u64 nd  | nd x digest 32 | u64 44 | requestor b64 (44)
+ * (bincode 1.x, fixint, little endian; bytes after a complete message are
+ * allowed; csrc/wmsg_plan.hpp).  A batch with no transaction is valid, and so
+ * is a transaction of length 0.  The digest covers all len[i] bytes, trailing
+ * bytes included: the Processor hashes the bytes it was handed, not the part
+ * the decoder consumed.
+ *
+ * NT_WMSG_SERIALIZATION (the value of SerializationError among NT_DAG_*):
+ * bincode fails on the structure -- len < 4, a tag above 1, no room for the
+ * count, a count that cannot fit in the bytes left (8 per transaction, 32 per
+ * digest), a length prefix or string that runs past len (prefixes near 2^64
+ * included: nothing is added before it is compared).  Unlike the primary's
+ * calls this one gives that verdict itself; the reference logs and drops such
+ * a message.  NT_WMSG_HOST: the device does not decide, the caller runs its
+ * host decoder -- a count that fits but is above the caps (2^20 request
+ * digests, 2^24 transactions); a requestor string whose length prefix is not
+ * 44, or whose 44 characters are not the canonical base64 text of 32 bytes
+ * (43 alphabet characters and '=', trailing bits zero). */
+#define NT_WMSG_OK 0
+#define NT_WMSG_SERIALIZATION 9
+#define NT_WMSG_HOST 0xff
+#define NT_WORKER_KIND_BATCH 0
+#define NT_WORKER_KIND_REQUEST 1
+#define NT_WORKER_KIND_NONE 0xff
+#define NT_WORKER_RECEIPT_UNIFORM 1u /* flags bit 0 */
+/* kind != 0xff exactly when code == NT_WMSG_OK; otherwise every byte after
+ * code and kind is zero.  Offsets are relative to the message's first byte.
+ * The natural C layout has no padding. */
+typedef struct nt_worker_receipt {
+  uint8_t code;       /* the byte out_code[i] gets */
+  uint8_t kind;       /* 0 batch, 1 batch request, 0xff = not decoded (HOST or SERIALIZATION) */
+  uint16_t flags;     /* bit 0: every transaction has the same length (ntx >= 1) */
+  uint32_t n;         /* batch: transactions; request: digests (at offset 12, 32 bytes each) */
+  uint64_t used;      /* bytes the decoder consumes (<= len; the rest is trailing) */
+  uint64_t tx_bytes;  /* batch: sum of the transaction lengths; request: 0 */
+  uint32_t tx_len;    /* the common length when flags bit 0 is set, else 0: transaction k is at
+                         12 + k * (8 + tx_len) + 8 */
+  uint32_t off_key;   /* request: offset of the 44-character requestor text; batch: 0 */
+  uint8_t digest[32]; /* OK batch: SHA-512(all len bytes)[..32]; OK request: the requestor's raw
+                         32-byte key; otherwise zero */
+} nt_worker_receipt;
+#if defined(__cplusplus)
+static_assert(sizeof(nt_worker_receipt) == 64, "nt_worker_receipt is 64 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nt_worker_receipt) == 64, "nt_worker_receipt is 64 bytes");
+#else /* C99 has no static assertion: an array type of size -1 does not compile */
+typedef char nt_worker_receipt_is_64_bytes[sizeof(nt_worker_receipt) == 64 ? 1 : -1];
+#endif
+/* message i = data[off[i] .. off[i] + len[i]), starting at any byte; out_code:
+ * n bytes; out_receipt: n records, or NULL (codes only: nothing is hashed).
+ * Borrowed host memory, synchronous, sharded by contiguous message ranges over
+ * the context's devices; inputs in nt_host_alloc memory are DMA'd in place.
+ * Chunks are cut by bytes and pipelined like the digest call's: the copy of
+ * one runs under the kernels of the previous one (one wave per message walks
+ * the layout, then the SHA-512 launch of nt_sha512_trunc32 over the same
+ * bytes).  With NT_SMALL_AUTO / NT_SMALL_ALWAYS the call routes as
+ * nt_sha512_trunc32 does for the same lengths, and the host lane runs the same
+ * walk.  n = 0 returns NT_OK and writes nothing.  A chunk holds at most 1,024 x
+ * the shard's longest message in bytes (64 MB at least, 1 GB at most) and 65,536
+ * messages.  NT_WINGEST_CHUNK (messages) and NT_WINGEST_CHUNK_BYTES override the
+ * two bounds: test hooks for forcing chunk seams, read at every call; a value
+ * that is not a positive integer is ignored. */
+int nt_worker_messages_ingest(nt_ctx *ctx, const uint8_t *data, const uint64_t *off, const uint64_t *len,
+                              uint64_t n, uint8_t *out_code, nt_worker_receipt *out_receipt);
+
 /* ---- small-call path (SURVEY.md H3, §8(b) "CPU-fallback threshold") ------
  * The reference calls verify once per header / vote, verify_batch once per
  * certificate (primary/src/core.rs:349-411) and hashes one ~508 KB batch per

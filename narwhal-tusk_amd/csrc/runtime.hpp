@@ -1,8 +1,8 @@
 // runtime.hpp -- the host runtime's internal types, shared by the C-ABI
 // translation units (context.cpp, calibrate.cpp, verify.cpp, groups.cpp,
 // keyset.cpp, sign.cpp, dev_api.cpp: one per family of entry points;
-// registry.cpp: the key registry; ingest_gpu.cpp: wire ingestion on the
-// device).  Not part of the ABI.
+// registry.cpp: the key registry; ingest_gpu.cpp, wingest_gpu.cpp: the primary's
+// and the worker's wire ingestion on the device).  Not part of the ABI.
 //
 // A context (nt_ctx) holds one Device per device entry; an entry holds extra
 // execution slots (Devices too) that share its tables.  A slot's per-stream state
@@ -241,6 +241,8 @@ struct Device {
   std::vector<std::unique_ptr<Device>> extra;
   // state of the wire-ingestion entry point on this slot (ingest_gpu.cpp), created on first use
   std::shared_ptr<void> ingest;
+  // ... and of the worker's (wingest_gpu.cpp)
+  std::shared_ptr<void> wingest;
 
   // The buffers free themselves (after this body).  What needs an order: the streams drained
   // first, and the extra slots gone before this entry's comb of B and x table, which they borrow.

@@ -201,6 +201,59 @@ void ntn_batcher_stats(void* b, double out[4]) {
   out[3] = s.hash_seconds;
 }
 
+// ---- the worker's drain ----------------------------------------------------
+// worker::decode_message, the plain host decoder: the kind (0 batch, 1 request) or -1 on a
+// bincode error; out3 = count (transactions / digests), bytes consumed, sum of the
+// transaction lengths; key32 = a request's requestor.
+int ntn_worker_decode(const uint8_t* data, uint64_t len, uint64_t* out3, uint8_t* key32) {
+  try {
+    worker::WorkerMessage m;
+    size_t used = 0;
+    if (!worker::decode_message(data, (size_t)len, m, &used)) return -1;
+    const bool batch = m.kind == worker::WorkerMessage::Kind::Batch;
+    uint64_t bytes = 0;
+    for (const auto& tx : m.batch) bytes += tx.size();
+    out3[0] = batch ? m.batch.size() : m.digests.size();
+    out3[1] = used;
+    out3[2] = bytes;
+    if (!batch) std::memcpy(key32, m.requestor.bytes.data(), 32);
+    return batch ? 0 : 1;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+
+// worker::ingest_device over n packed wire messages.  Per message: out_codes (NT_WMSG_OK /
+// NT_WMSG_SERIALIZATION), out_kinds (0 batch, 1 request; 0xff when the code is not OK),
+// out_msg40 (a batch: the Processor's 40-byte OthersBatch(digest, worker_id); else zero),
+// out_key32 (a request's requestor; else zero), out_nd (a request's digests), and
+// out_receipts, the n 64-byte records (nt_worker_receipt) as the device wrote them.
+// Returns 0, or -2 on a backend failure.
+int ntn_worker_ingest(uint32_t worker_id, const uint8_t* data, const uint64_t* off, const uint64_t* len, uint64_t n,
+                      uint8_t* out_codes, uint8_t* out_kinds, uint8_t* out_msg40, uint8_t* out_key32,
+                      uint32_t* out_nd, uint8_t* out_receipts, uint64_t* host_decided) {
+  try {
+    size_t host = 0;
+    const auto r = worker::ingest_device(worker_id, data, off, len, (size_t)n, (nt_worker_receipt*)out_receipts, &host);
+    std::memset(out_msg40, 0, 40 * (size_t)n);
+    std::memset(out_key32, 0, 32 * (size_t)n);
+    for (uint64_t i = 0; i < n; ++i) {
+      out_codes[i] = r[i].code;
+      out_kinds[i] = r[i].code == NT_WMSG_OK ? (uint8_t)r[i].kind : (uint8_t)NT_WORKER_KIND_NONE;
+      out_nd[i] = (uint32_t)r[i].digests.size();
+      if (r[i].code != NT_WMSG_OK) continue;
+      if (r[i].kind == worker::WorkerMessage::Kind::Batch)
+        std::memcpy(out_msg40 + 40 * i, r[i].message.data(), std::min<size_t>(40, r[i].message.size()));
+      else
+        std::memcpy(out_key32 + 32 * i, r[i].requestor.bytes.data(), 32);
+    }
+    if (host_decided) *host_decided = host;
+    return 0;
+  } catch (const std::exception&) {
+    return -2;
+  }
+}
+
 // the small-call path of the mirror's shared context (include/ntcrypto.h)
 int ntn_set_small_call_path(int mode, int threads) {
   try {

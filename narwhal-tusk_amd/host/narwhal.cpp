@@ -567,4 +567,100 @@ std::vector<uint8_t> Processor::process(const std::vector<uint8_t>& serialized_b
   return processor_message(*this, d);
 }
 
+// bincode::deserialize::<WorkerMessage> (worker.rs:278): u32 variant, then the variant's
+// fields in order; a sequence is read element by element, so a count the bytes cannot hold
+// fails when they run out.
+bool decode_message(const uint8_t* p, size_t n, WorkerMessage& out, size_t* used) {
+  size_t pos = 0;
+  auto u64 = [&](uint64_t& x) {
+    if (n - pos < 8) return false;
+    std::memcpy(&x, p + pos, 8);  // little endian hosts only, like the rest of the mirror
+    pos += 8;
+    return true;
+  };
+  if (n < 4) return false;
+  uint32_t tag;
+  std::memcpy(&tag, p, 4);
+  pos = 4;
+  uint64_t cnt;
+  if (tag > 1 || !u64(cnt)) return false;
+  out = WorkerMessage{};
+  if (tag == 0) {
+    out.kind = WorkerMessage::Kind::Batch;
+    if (cnt > (n - pos) / 8) return false;
+    out.batch.reserve((size_t)cnt);
+    for (uint64_t k = 0; k < cnt; ++k) {
+      uint64_t len;
+      if (!u64(len) || len > n - pos) return false;
+      out.batch.emplace_back(p + pos, p + pos + len);
+      pos += (size_t)len;
+    }
+  } else {
+    out.kind = WorkerMessage::Kind::BatchRequest;
+    if (cnt > (n - pos) / 32) return false;
+    out.digests.resize((size_t)cnt);
+    for (auto& d : out.digests) {
+      std::memcpy(d.bytes.data(), p + pos, 32);
+      pos += 32;
+    }
+    uint64_t klen;
+    if (!u64(klen) || klen > n - pos) return false;
+    if (!primary::decode_public_key(p + pos, (size_t)klen, out.requestor)) return false;
+    pos += (size_t)klen;
+  }
+  if (used) *used = pos;
+  return true;
+}
+
+std::vector<Ingested> ingest_device(uint32_t worker_id, const uint8_t* data, const uint64_t* off, const uint64_t* len,
+                                    size_t n, nt_worker_receipt* receipts, size_t* host_decided) {
+  std::vector<Ingested> res(n);
+  if (host_decided) *host_decided = 0;
+  if (n == 0) return res;
+  std::vector<uint8_t> code(n);
+  std::vector<nt_worker_receipt> own;
+  if (!receipts) {
+    own.resize(n);
+    receipts = own.data();
+  }
+  const int rc = nt_worker_messages_ingest(crypto::Backend::global().ctx(), data, off, len, n, code.data(), receipts);
+  if (rc != NT_OK) throw crypto::BackendError(std::string("nt_worker_messages_ingest failed: ") + nt_strerror(rc));
+  const Processor proc{worker_id, false};
+  size_t host = 0;
+  for (size_t i = 0; i < n; ++i) {
+    Ingested& r = res[i];
+    const nt_worker_receipt& rec = receipts[i];
+    const uint8_t* m = data + off[i];
+    r.code = code[i];
+    if (code[i] == NT_WMSG_OK && rec.kind == NT_WORKER_KIND_BATCH) {
+      r.kind = WorkerMessage::Kind::Batch;
+      std::memcpy(r.digest.bytes.data(), rec.digest, 32);
+      r.message = processor_message(proc, r.digest);
+    } else if (code[i] == NT_WMSG_OK) {  // the digests lie in the message, the key in the receipt
+      r.kind = WorkerMessage::Kind::BatchRequest;
+      r.digests.resize(rec.n);
+      for (uint32_t k = 0; k < rec.n; ++k) std::memcpy(r.digests[k].bytes.data(), m + 12 + 32 * (size_t)k, 32);
+      std::memcpy(r.requestor.bytes.data(), rec.digest, 32);
+    } else if (code[i] == NT_WMSG_HOST) {  // oddities only: the plain decoder, and for a batch the plain digest
+      ++host;
+      WorkerMessage wm;
+      if (!decode_message(m, (size_t)len[i], wm)) {
+        r.code = NT_WMSG_SERIALIZATION;
+        continue;
+      }
+      r.code = NT_WMSG_OK;
+      r.kind = wm.kind;
+      if (wm.kind == WorkerMessage::Kind::Batch) {
+        r.digest = crypto::sha512_digest(m, (size_t)len[i]);
+        r.message = processor_message(proc, r.digest);
+      } else {
+        r.digests = std::move(wm.digests);
+        r.requestor = wm.requestor;
+      }
+    }
+  }
+  if (host_decided) *host_decided = host;
+  return res;
+}
+
 }  // namespace worker

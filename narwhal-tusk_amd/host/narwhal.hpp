@@ -13,6 +13,8 @@
 //   worker::serialize_batch / batch_digest / Processor / DigestBatcher
 //                                           worker/src/batch_maker.rs:117-119,
 //                                           worker/src/processor.rs:35-55 (§8(f).3)
+//   worker::decode_message / ingest_device  worker/src/worker.rs:270-292: the receiver's
+//                                           decode, on the host and on the device
 #pragma once
 #include <condition_variable>
 #include <cstdint>
@@ -29,6 +31,7 @@
 #include "crypto.hpp"
 
 struct nt_msg_receipt;  // include/ntcrypto.h
+struct nt_worker_receipt;
 
 namespace primary {
 
@@ -264,5 +267,37 @@ class DigestBatcher {
   Stats stats_;
   std::thread th_;
 };
+
+// WorkerMessage (worker/src/worker.rs:39-43): what one worker sends another.
+struct WorkerMessage {
+  enum class Kind : uint32_t { Batch = 0, BatchRequest = 1 };
+  Kind kind = Kind::Batch;
+  Batch batch;                          // Batch
+  std::vector<crypto::Digest> digests;  // BatchRequest
+  crypto::PublicKey requestor;          // BatchRequest
+};
+// The plain host decoder of both variants, field by field as bincode reads them (a batch
+// builds its Vec<Vec<u8>>): false = a bincode error; `used` = bytes consumed.  What a
+// receiver runs on every message today (worker.rs:278), and the fallback for the messages
+// nt_worker_messages_ingest leaves to the host (NT_WMSG_HOST).
+bool decode_message(const uint8_t* p, size_t n, WorkerMessage& out, size_t* used = nullptr);
+
+// One message of a drain put through nt_worker_messages_ingest: what the receiver's two
+// handlers need (worker.rs:278-291).  A batch: the Processor's output for it (processor.rs:
+// 36-48, `message` = the 40-byte bincode OthersBatch(digest, id)).  A request: its digests
+// and the requestor.  code: NT_WMSG_OK or NT_WMSG_SERIALIZATION -- a message the device left
+// to the host (NT_WMSG_HOST) has been through decode_message.
+struct Ingested {
+  uint8_t code = 9;
+  WorkerMessage::Kind kind = WorkerMessage::Kind::Batch;
+  crypto::Digest digest;
+  std::vector<uint8_t> message;
+  std::vector<crypto::Digest> digests;
+  crypto::PublicKey requestor;
+};
+// receipts (nullable): the n records as the device wrote them; host_decided (nullable): the
+// count of messages decode_message decided.  Throws crypto::BackendError on a backend failure.
+std::vector<Ingested> ingest_device(uint32_t worker_id, const uint8_t* data, const uint64_t* off, const uint64_t* len,
+                                    size_t n, nt_worker_receipt* receipts = nullptr, size_t* host_decided = nullptr);
 
 }  // namespace worker

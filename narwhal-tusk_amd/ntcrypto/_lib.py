@@ -37,7 +37,7 @@ EXPORTED = [
     "nt_committee_create", "nt_committee_free", "nt_certificates_ingest", "nt_small_call_model",
     "nt_set_hbm_budget", "nt_memory_info", "nt_dev_stream", "nt_set_key_cache", "nt_key_cache_add",
     "nt_key_cache_sync", "nt_key_cache_info", "nt_dev_clock_probe", "nt_dev_ed25519_verify_keyset_groups",
-    "nt_primary_messages_ingest", "nt_primary_messages_ingest_receipts",
+    "nt_primary_messages_ingest", "nt_primary_messages_ingest_receipts", "nt_worker_messages_ingest",
 ]
 # nt_msg_receipt (include/ntcrypto.h): one 128-byte record per ingested message
 RECEIPT_DTYPE = np.dtype({
@@ -49,6 +49,16 @@ RECEIPT_DTYPE = np.dtype({
     "itemsize": 128,
 })
 RECEIPT_KIND_HOST = 0xFF
+# nt_worker_receipt (include/ntcrypto.h): one 64-byte record per ingested worker message
+WORKER_RECEIPT_DTYPE = np.dtype({
+    "names": ["code", "kind", "flags", "n", "used", "tx_bytes", "tx_len", "off_key", "digest"],
+    "formats": ["u1", "u1", "<u2", "<u4", "<u8", "<u8", "<u4", "<u4", ("u1", 32)],
+    "offsets": [0, 1, 2, 4, 8, 16, 24, 28, 32],
+    "itemsize": 64,
+})
+WMSG_OK, WMSG_SERIALIZATION, WMSG_HOST = 0, 9, 0xFF
+WORKER_KIND_BATCH, WORKER_KIND_REQUEST, WORKER_KIND_NONE = 0, 1, 0xFF
+WORKER_RECEIPT_UNIFORM = 1    # flags bit 0
 RECEIPT_GENESIS = 1           # flags bit 0
 KEY_CACHE_INFO_KEYS = ("keys", "max_keys", "comb_bits", "bytes_per_device", "hits", "misses", "admitted", "refused",
                        "pending", "error", "alloc_us", "build_us")
@@ -118,6 +128,8 @@ def load_library(path=None):
     if hasattr(lib, "nt_primary_messages_ingest_receipts"):  # absent from older A/B builds (NTCRYPTO_LIB)
         lib.nt_primary_messages_ingest_receipts.argtypes = [_vp, _vp, _u8p, _u64p, _u64p, _u64, _u64, _u8p, _u64, _u8p,
                                                             _u8p, _vp]
+    if hasattr(lib, "nt_worker_messages_ingest"):  # absent from older A/B builds (NTCRYPTO_LIB)
+        lib.nt_worker_messages_ingest.argtypes = [_vp, _u8p, _u64p, _u64p, _u64, _u8p, _vp]
     if hasattr(lib, "nt_memory_info"):  # absent from round-3 A/B builds (NTCRYPTO_LIB)
         lib.nt_set_hbm_budget.argtypes = [_vp, ctypes.c_uint64]
         lib.nt_memory_info.argtypes = [_vp, ctypes.c_int, _u64p]
@@ -304,6 +316,48 @@ class Backend:
         off = np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.uint64) if len(messages) else np.zeros(0, np.uint64)
         data = np.frombuffer(b"".join(messages), np.uint8) if messages else np.zeros(0, np.uint8)
         return self.sha512_trunc32(data, off, ln)
+
+    # ---- the worker's drain ----
+    def ingest_worker_messages(self, messages, receipts=True, data=None, off=None, ln=None):
+        """The worker's drain on the device (nt_worker_messages_ingest): bincode
+        WorkerMessage bytes, batches and requests alike.  Returns the codes
+        (WMSG_OK, WMSG_SERIALIZATION, WMSG_HOST = left to the host decoder) and,
+        with receipts=True, a WORKER_RECEIPT_DTYPE array: a batch's record carries
+        the Processor's digest.  An array passed as `receipts` (n records,
+        C-contiguous) is filled in place and returned; receipts=False returns the
+        codes alone (nothing is hashed).  messages: a list of byte strings, or
+        None with data / off / ln already packed (data may be a Backend.pinned
+        array: it is then DMA'd in place)."""
+        if messages is not None:
+            n = len(messages)
+            ln = np.array([len(m) for m in messages], np.uint64)
+            off = np.zeros(n, np.uint64)
+            if n > 1:
+                off[1:] = np.cumsum(ln)[:-1]
+            data = np.frombuffer(b"".join(messages), np.uint8) if n else np.zeros(1, np.uint8)
+        else:
+            off = np.ascontiguousarray(off, np.uint64)
+            ln = np.ascontiguousarray(ln, np.uint64)
+            n = len(off)
+            if len(ln) != n or data.dtype != np.uint8 or not data.flags.c_contiguous:
+                raise ValueError("data: C-contiguous uint8; off and ln: one entry per message")
+            size = np.uint64(len(data))          # compared before anything is added: uint64 sums wrap
+            if n and (bool((off > size).any()) or bool((ln > size - np.minimum(off, size)).any())):
+                raise ValueError("a message reaches past the end of data")
+        data = data if len(data) else np.zeros(1, np.uint8)
+        out = np.zeros(max(n, 1), np.uint8)
+        if receipts is False or receipts is None:
+            rec = None
+        elif receipts is True:
+            rec = np.zeros(max(n, 1), WORKER_RECEIPT_DTYPE)
+        else:
+            rec = receipts
+            if rec.dtype != WORKER_RECEIPT_DTYPE or rec.ndim != 1 or len(rec) != n or not rec.flags.c_contiguous:
+                raise ValueError("receipts: a C-contiguous WORKER_RECEIPT_DTYPE array of one record per message")
+        _check(self.lib.nt_worker_messages_ingest(self.ctx, _p(data), _p(off, _u64p), _p(ln, _u64p), n, _p(out),
+                                                  rec.ctypes.data_as(_vp) if rec is not None and n else None),
+               "nt_worker_messages_ingest")
+        return out[:n] if rec is None else (out[:n], rec[:n])
 
     # ---- Ed25519 ----
     def verify_strict(self, pk, sig, msg, off, ln):

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._lib import PKG_ROOT, RECEIPT_DTYPE, NtError
+from ._lib import PKG_ROOT, RECEIPT_DTYPE, WORKER_RECEIPT_DTYPE, NtError
 
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libntnarwhal.so")
 DAG_ERRORS = ["Ok", "InvalidSignature", "InvalidHeaderId", "MalformedHeader", "UnknownAuthority",
@@ -66,6 +66,11 @@ def load():
         lib.ntn_batcher_stats.restype = None
         lib.ntn_set_small_call_path.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.ntn_set_small_call_path.restype = ctypes.c_int
+        lib.ntn_worker_decode.argtypes = [_u8p, ctypes.c_uint64, _u64p, _u8p]
+        lib.ntn_worker_decode.restype = ctypes.c_int
+        lib.ntn_worker_ingest.argtypes = [ctypes.c_uint32, _u8p, _u64p, _u64p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p,
+                                          _u32p, ctypes.c_void_p, _u64p]
+        lib.ntn_worker_ingest.restype = ctypes.c_int
         _lib = lib
     return _lib
 
@@ -195,6 +200,45 @@ def set_small_call_path(mode, threads=0):
     rc = load().ntn_set_small_call_path(int(mode), int(threads))
     if rc != 0:
         raise NtError("ntn_set_small_call_path failed (%d)" % rc)
+
+
+def worker_decode(msg: bytes):
+    """worker::decode_message, the plain host decoder of a bincode WorkerMessage (CPU only):
+    None on a bincode error, else a dict -- kind (0 batch, 1 request), n (transactions /
+    digests), used (bytes consumed), tx_bytes, requestor (a request's raw key, else None)."""
+    a, p = _buf(msg)
+    out = (ctypes.c_uint64 * 3)()
+    key = np.zeros(32, np.uint8)
+    kind = load().ntn_worker_decode(p, len(msg), out, key.ctypes.data_as(_u8p))
+    if kind < 0:
+        return None
+    return {"kind": kind, "n": int(out[0]), "used": int(out[1]), "tx_bytes": int(out[2]),
+            "requestor": key.tobytes() if kind == 1 else None}
+
+
+def worker_ingest(worker_id, messages):
+    """worker::ingest_device: the drain of a worker through nt_worker_messages_ingest, the
+    messages it leaves to the host through worker::decode_message.  Returns a dict of
+    arrays with one row per message -- code (0 / 9), kind (0 batch, 1 request, 0xff),
+    message (a batch: the Processor's 40-byte OthersBatch(digest, worker_id)), requestor,
+    nd -- plus receipts (WORKER_RECEIPT_DTYPE, as the device wrote them) and host_decided."""
+    data, off, ln = pack(messages)
+    n = len(messages)
+    m = max(n, 1)
+    codes, kinds = np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+    msg40, key32 = np.zeros((m, 40), np.uint8), np.zeros((m, 32), np.uint8)
+    nd = np.zeros(m, np.uint32)
+    rec = np.zeros(m, WORKER_RECEIPT_DTYPE)
+    host = ctypes.c_uint64(0)
+    data = data if len(data) else np.zeros(1, np.uint8)
+    rc = load().ntn_worker_ingest(int(worker_id), data.ctypes.data_as(_u8p), off.ctypes.data_as(_u64p),
+                                  ln.ctypes.data_as(_u64p), n, codes.ctypes.data_as(_u8p), kinds.ctypes.data_as(_u8p),
+                                  msg40.ctypes.data_as(_u8p), key32.ctypes.data_as(_u8p), nd.ctypes.data_as(_u32p),
+                                  rec.ctypes.data_as(ctypes.c_void_p), ctypes.byref(host))
+    if rc != 0:
+        raise NtError("ntn_worker_ingest: backend failure")
+    return {"code": codes[:n], "kind": kinds[:n], "message": msg40[:n], "requestor": key32[:n], "nd": nd[:n],
+            "receipts": rec[:n], "host_decided": int(host.value)}
 
 
 class DigestBatcher:
