@@ -108,6 +108,11 @@ const char *nt_version(void);
  *   out8[2] key-comb bytes of live key sets             out8[3] verify workspaces
  *   out8[4] key-cache stashes + sort scratch            out8[5] other device staging
  *   out8[6] the budget (0 = none)                       out8[7] table bytes held against it */
+/* nt_memory_info(ctx, dev | NT_INFO_KTAB, out8): the key-table cache, see nt_dev_ed25519_verify.
+ * A stop-gap: a flag in an ordinal is a surprising interface.  An export of its own
+ * (nt_ktab_info) should replace it, together with the change to the ABI test that pins the
+ * export list, in a change of its own. */
+#define NT_INFO_KTAB 0x10000
 int nt_set_hbm_budget(nt_ctx *ctx, uint64_t bytes_per_device);
 int nt_memory_info(nt_ctx *ctx, int dev, uint64_t *out8);
 
@@ -489,6 +494,17 @@ void nt_host_free(void *p);
  * square root again.  Verdicts do not depend on the table -- an entry is used
  * only when it is proven to be the key's x -- and rates do: a batch whose keys
  * this context has verified before runs about 6 % faster.
+ *
+ * The same kernel keeps, for a key it meets a second time, the window tables of
+ * A, [2^64]A and [2^128]A in a pool per device entry (NT_KTAB_KEYS entries of
+ * 3,968 bytes, default 2^20, halved down to 2^14 while the HBM budget or the
+ * device does not allow it; 0 = off; read again at every launch) and verifies
+ * later signatures of that key with a ladder of half the doublings.  Entries are
+ * only added, never replaced, until the context closes.  Verdicts do not depend
+ * on the pool.  nt_memory_info(ctx, dev | NT_INFO_KTAB, out8), after the launches
+ * of interest have completed: out8[0] entries in use, out8[1] capacity, out8[2] device bytes,
+ * out8[3] wave rows (64 signatures) that took the short ladder, out8[4] rows
+ * that built entries, out8[5] rows on the balanced path, out8[6] index slots.
  *
  * nt_dev_stream returns device entry `dev`'s two compute streams (which = 0 /
  * 1), the streams the host entry points pipeline on: non-blocking, ordered

@@ -176,11 +176,79 @@ static void xcache_for(Device& dv) {
   dv.xtab_ready.store(1, std::memory_order_release);
 }
 
+// The key-table cache of execution slot dv: its entry's, allocated by the entry's first verify that
+// finds NT_KTAB_KEYS non-zero -- after the comb of B and the x cache -- at that many pool entries
+// (default 2^20 = 4.16 GB) beside an index of 2^21 slots (16 MB) and the control block, both
+// zero-filled, and reserved in the entry's HBM budget.  The default halves down to 2^14 entries
+// while the budget (the cache keeps to 1/16 of a finite one: the rest is the combs') or the device
+// (the comb's rule: 4 GB stay free) does not allow it; a size asked
+// for by NT_KTAB_KEYS is tried as it is.  A cache that fits nowhere is skipped silently: the
+// kernel then runs every verification on the balanced path as before.
+// words 4..6 of the control block: the pool's address and the index mask (read by every launch)
+static hipError_t ktab_describe(void* base, void* pool) {
+  uint32_t w[3];
+  const uint64_t a = (uint64_t)(uintptr_t)pool;
+  w[0] = (uint32_t)a;
+  w[1] = (uint32_t)(a >> 32);
+  w[2] = nt::kKTabIndexSlots - 1;
+  return hipMemcpy((uint8_t*)base + 16, w, sizeof w, hipMemcpyHostToDevice);
+}
+static void ktab_for(Device& dv) {
+  if (dv.ktab_ready.load(std::memory_order_acquire)) return;
+  Device& e = *dv.entry;
+  std::lock_guard<std::mutex> lk(e.tables_mu);
+  if (!e.ktab_tried) {
+    unsigned long long want = nt::kKTabKeysDefault;
+    const char* v = std::getenv("NT_KTAB_KEYS");
+    if (v) want = std::min<unsigned long long>(std::strtoull(v, nullptr, 10), 1ull << 26);
+    if (!want) return;  // off for this launch: the first one that asks for a cache allocates it
+    e.ktab_tried = true;
+    const uint64_t index_bytes = nt::kKTabCtlBytes + 8ull * nt::kKTabIndexSlots;
+    hipStream_t s = dv.lane[0].stream;
+    // Under a budget the cache keeps to 1/16 of it: what the budget leaves after the comb of B is
+    // the key combs', whose width decides the rate of every key-cache launch.
+    uint64_t share = ~0ull;
+    {
+      std::lock_guard<std::mutex> g(e.budget->mu);
+      if (e.budget->limit) share = e.budget->limit / 16;
+    }
+    for (uint64_t keys = want; keys >= 1; keys /= 2) {
+      const uint64_t bytes = index_bytes + keys * nt::ktab_entry_bytes();
+      size_t fr = 0, tot = 0;
+      if (hipSetDevice(e.ordinal) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) break;
+      if (bytes <= share && fr >= bytes + kCombHeadroom && e.budget->reserve_aux(bytes)) {
+        void *ps = nullptr, *pp = nullptr;
+        if (hipMalloc(&ps, index_bytes) == hipSuccess && hipMalloc(&pp, keys * nt::ktab_entry_bytes()) == hipSuccess &&
+            hipMemsetAsync(ps, 0, index_bytes, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
+            ktab_describe(ps, pp) == hipSuccess) {
+          e.d_kslots = ps;
+          e.d_kpool = pp;
+          e.kcap = (uint32_t)keys;
+          e.ktab_reserved = bytes;
+          break;
+        }
+        (void)hipGetLastError();
+        if (ps) (void)hipFree(ps);
+        if (pp) (void)hipFree(pp);
+        e.budget->release_aux(bytes);
+      }
+      if (v || keys / 2 < nt::kKTabKeysFloor) break;
+    }
+  }
+  if (&dv != &e) {
+    dv.d_kslots = e.d_kslots;
+    dv.d_kpool = e.d_kpool;
+    dv.kcap = e.kcap;
+  }
+  dv.ktab_ready.store(1, std::memory_order_release);
+}
+
 // everything the verify kernel of slot dv reads besides its inputs; lane 0's [k]A workspace at
 // its full ws_slots slots (before a call's copies start, not at its first launch)
 int verify_tables(Device& dv) {
   NT_CHK(comb_b_for(dv));
   xcache_for(dv);
+  ktab_for(dv);
   return Device::grow_synced(dv.lane[0].ws, nt::ws_bytes_per_slot() * dv.ws_slots, dv.lane[0].ws_done);
 }
 
@@ -385,7 +453,35 @@ int nt_set_hbm_budget(nt_ctx* ctx, uint64_t bytes_per_device) {
   return NT_OK;
 }
 
+// nt_memory_info(ctx, dev | NT_INFO_KTAB, out8): the key-table cache of device entry `dev`
+static int ktab_info(nt_ctx* ctx, int dev, uint64_t* out8) {
+  if (!ctx || !out8 || dev < 0 || dev >= (int)ctx->devs.size()) return NT_EINVAL;
+  Device& e = *ctx->devs[dev];
+  uint64_t v[8] = {};
+  void* slots = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(e.tables_mu);
+    slots = e.d_kslots;
+    v[1] = e.kcap;
+    v[2] = e.ktab_reserved;
+    v[6] = slots ? nt::kKTabIndexSlots : 0;
+  }
+  if (slots) {
+    uint32_t ctl[nt::kKTabCtlWords] = {};
+    if (hipSetDevice(e.ordinal) != hipSuccess ||
+        hipMemcpy(ctl, slots, sizeof ctl, hipMemcpyDeviceToHost) != hipSuccess)
+      return NT_EHIP;
+    v[0] = std::min<uint64_t>(ctl[0], v[1]);  // the bump counter may run past a full pool
+    v[3] = ctl[1];
+    v[4] = ctl[2];
+    v[5] = ctl[3];
+  }
+  std::memcpy(out8, v, sizeof v);
+  return NT_OK;
+}
+
 int nt_memory_info(nt_ctx* ctx, int dev, uint64_t* out8) {
+  if (dev >= 0 && (dev & NT_INFO_KTAB)) return ktab_info(ctx, dev & ~NT_INFO_KTAB, out8);
   if (!ctx || !out8 || dev < 0 || dev >= (int)ctx->devs.size()) return NT_EINVAL;
   Device& e = *ctx->devs[dev];
   uint64_t ws = 0, stash = 0, staging = 0;

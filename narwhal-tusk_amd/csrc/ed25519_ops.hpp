@@ -5,6 +5,7 @@
 //          (load_signed: entry e0 + |d|, negated when d < 0)
 //   WComb: load(pos, idx, ge_niels&)                            idx * 2^(16 pos) * P (wide comb)
 //   XCache: load(slot, words) / store(slot, words)              decompressed x of keys seen before (NoXCache: none)
+//   KTab:   the window tables of A, [2^64]A, [2^128]A of keys seen before (NoKTab: none; see KTab below)
 //
 // Semantics (restated from ed25519-dalek 1.0.1 /
 // curve25519-dalek 3.x):
@@ -547,9 +548,20 @@ NT_HD NT_INLINE uint32_t xcache_cand(uint32_t b0, uint32_t b1, uint32_t c, uint3
 // same for one lane as for 64); otherwise the whole wave decompresses as before,
 // and the lanes that found nothing leave their x (when the key decodes and
 // x != 0) for the next call.
-template <class XCache>
-NT_HD NT_INLINE uint32_t ge_frombytes_cached(ge_p3& A, const uint32_t Aw[8], const XCache& xc) {
-  if (!XCache::kEnabled) return ge_frombytes_w(A, Aw);
+// seen(known): told, once per call, what the x cache knows of this lane's key.  2: its x was
+// found -- the key has been met before.  1: nothing can be said (no table, or a key the table can
+// never hold: it does not decode, or x = 0).  0: the first sighting of a key the table will know
+// next time.  The key-table cache takes its first-sighting record from here (NoSeen: nobody asks).
+struct NoSeen {
+  NT_HD NT_INLINE void operator()(uint32_t) const {}
+};
+template <class XCache, class Seen = NoSeen>
+NT_HD NT_INLINE uint32_t ge_frombytes_cached(ge_p3& A, const uint32_t Aw[8], const XCache& xc,
+                                             const Seen& seen = Seen()) {
+  if (!XCache::kEnabled) {
+    seen(1u);
+    return ge_frombytes_w(A, Aw);
+  }
   const bool have = xc.active();
   const uint32_t mask = have ? xc.mask() : 0u;
   const uint32_t h0 = xcache_hash(Aw, 0x9e3779b9u), h1 = xcache_hash(Aw, 0x7f4a7c15u);
@@ -560,7 +572,7 @@ NT_HD NT_INLINE uint32_t ge_frombytes_cached(ge_p3& A, const uint32_t Aw[8], con
   ge_frombytes_uv(A, u, v, Aw);
   fe_0(A.X);
   constexpr uint32_t kNone = kXWays;
-  uint32_t hit = 0, ok = 1, used0 = 0, used1 = 0, free0 = kNone, free1 = kNone;
+  uint32_t hit = 0, ok = 1, used0 = 0, used1 = 0, free0 = kNone, free1 = kNone, fresh = 0;
   if (have) {
 #pragma unroll 1
     for (uint32_t c = 0; c < kXCand; ++c) {
@@ -595,6 +607,7 @@ NT_HD NT_INLINE uint32_t ge_frombytes_cached(ge_p3& A, const uint32_t Aw[8], con
 #pragma unroll
       for (int i = 0; i < 8; ++i) nz |= xw[i];
       if (nz) {
+        fresh = 1;
         const bool full = free0 == kNone && free1 == kNone;
         const bool second = full ? (h1 >> 31) != 0 : (free0 == kNone || (free1 != kNone && used1 < used0));
         const uint32_t fr = second ? free1 : free0;
@@ -603,6 +616,7 @@ NT_HD NT_INLINE uint32_t ge_frombytes_cached(ge_p3& A, const uint32_t Aw[8], con
       }
     }
   }
+  seen(fresh ? 0u : (hit ? 2u : 1u));
   ge_frombytes_t(A);
   return ok;
 }
@@ -611,14 +625,14 @@ NT_HD NT_INLINE uint32_t ge_frombytes_cached(ge_p3& A, const uint32_t Aw[8], con
 // max(bitlen |u|, bitlen v) <= bits; any valid vector gives the same verdict
 // (verify_one below uses sc_halfsize's; the tests also run the trivial (k, 1)).
 // xc: the x cache of A (R is fresh in every signature and never probed).
-template <int MODE, class ATab, class WComb, class XCache = NoXCache>
+template <int MODE, class ATab, class WComb, class XCache = NoXCache, class Seen = NoSeen>
 NT_HD NT_INLINE uint32_t verify_uv(const uint32_t Aw[8], const uint32_t Rw[8], const uint32_t Sw[8],
                                    const uint32_t u[8], uint32_t uneg, const uint32_t v[8], int bits, ATab& at,
-                                   const WComb& wb, const XCache& xc = XCache()) {
+                                   const WComb& wb, const XCache& xc = XCache(), const Seen& seen = Seen()) {
   uint32_t ok = sc_is_canonical(Sw);
   {
     ge_p3 A;
-    ok &= ge_frombytes_cached(A, Aw, xc);
+    ok &= ge_frombytes_cached(A, Aw, xc, seen);
     if (MODE == kStrict) ok &= ge_is_small_order_affine(A) ^ 1u;
     ptab_build(A, uneg ^ 1u, at, 0);  // -[u]A = [|u|](u < 0 ? A : -A)
   }
@@ -641,31 +655,407 @@ NT_HD NT_INLINE uint32_t verify_uv(const uint32_t Aw[8], const uint32_t Rw[8], c
   return ok & fe_iszero(acc.X) & fe_eq(acc.Y, acc.Z);
 }
 
+// ---------------------------------------------------------------------------
+// The key-table cache (KTab): for a public key this context has seen before,
+// the window tables j * P, j = 1..8, of P = A, A' = [2^64]A and A'' = [2^128]A,
+// kept across calls.  With them the lattice vector need not be balanced:
+// |u| ~ 2^192, v ~ 2^64 (sc_unbalanced), the 4-bit digits of |u| split into three
+// strings of 16 over the three tables, and the joint ladder is ~17 windows of
+// 4 doublings + 4 additions instead of ~33 of 4 + 2 (verify_uv3).  [u]A =
+// [u0]A + [u1]A' + [u2]A'' is an integer identity (A', A'' come from real
+// doublings of A), so the verdict is verify_uv's for every input.
+//
+// Storage (the verify kernel: DevKTab, kernels_common.hpp; the host harness: plain
+// memory and host atomics):
+//   pool   entries of kKtEntryBytes: a 128-B header (the 32 key bytes as tag,
+//          kKt* flags) + 3 tables x 8 cached points of 160 B.  Insert-only: an
+//          entry is handed out once by a bump counter and never rewritten or
+//          freed while the context lives.
+//   index  8-byte slots {fingerprint32, state32}; a key has two buckets of
+//          kKtBucket slots (half a 128-B line each) from two hashes.
+//   state  0 empty -> kKtSeen (first sighting: one CAS, nothing else)
+//          -> kKtClaimed (second sighting: CAS, one winner per key, who builds
+//          the entry after its verification) -> kKtReady0 + entry index.
+//          Pool exhausted: the slot stays kKtSeen.
+// Soundness.  A pool line is never read before the slot that names it has been
+// read as ready, the builder stores the whole entry, drains, releases at agent
+// scope and only then stores the slot word, and the reader acquires at agent
+// scope between the slot loads and the first pool load: together with
+// insert-only this means a reader sees either no entry or the finished one.  A
+// stale slot read is only a miss.  The header's full 32-byte tag is compared
+// before a table is used, so a fingerprint collision is a miss as well, and
+// every index is masked (slots) or bounds-checked (entries) before use.
+// A wave row takes the fast path only when all its lanes hit.
+//
+// Policy (KT):
+//   kEnabled, active(), slot_mask() (slots - 1, a power of two >= kKtBucket),
+//   capacity() (entries), slot_load / slot_cas / slot_store / slot_publish,
+//   acquire(), drain_release(), pool_used(), pool_take(), hdr_load / hdr_store,
+//   tab_store(idx, t, j, c), tab_load_signed(idx, t, d, c), count(which),
+//   claim_put / claim_get (what a lane owes the cache after its row, parked outside
+//   its registers while the balanced path runs), dig_put / dig_get (the 16 digit
+//   words of the three-table ladder, likewise)
+// ---------------------------------------------------------------------------
+constexpr uint32_t kKtTables = 3, kKtPerTable = 8;
+constexpr uint32_t kKtHeaderBytes = 128, kKtPointBytes = 160;
+constexpr uint32_t kKtEntryBytes = kKtHeaderBytes + kKtTables * kKtPerTable * kKtPointBytes;  // 3,968
+constexpr uint32_t kKtBucket = 8;             // slots per bucket (64 bytes)
+constexpr uint32_t kKtCand = 2 * kKtBucket;   // slots a probe reads
+constexpr uint32_t kKtSeen = 1, kKtClaimed = 2, kKtReady0 = 16;  // slot states; ready: kKtReady0 + index
+constexpr uint32_t kKtNoSlot = 0xffffffffu;
+constexpr uint32_t kKtWantMark = 0xfffffffeu;  // parked beside a claimed slot: mark this key after the row
+constexpr uint32_t kKtWantTake = 0xfffffffdu;  // ... or claim it outright: the x cache has met it before
+constexpr uint32_t kKtFlagShift = 28, kKtMaxEntries = 1u << kKtFlagShift;  // entry index | flags in one word
+enum : uint32_t { kKtUndecodable = 1u, kKtSmallOrder = 2u };  // header flags
+enum { kKtCntFast = 0, kKtCntBuild = 1, kKtCntOld = 2 };      // counters: wave rows
+
+struct NoKTab {
+  static constexpr bool kEnabled = false;
+  NT_HD NT_INLINE bool active() const { return false; }
+  NT_HD NT_INLINE uint32_t slot_mask() const { return 0; }
+  NT_HD NT_INLINE uint32_t capacity() const { return 0; }
+  NT_HD NT_INLINE uint64_t slot_load(uint32_t) const { return 0; }
+  NT_HD NT_INLINE uint64_t slot_cas(uint32_t, uint64_t, uint64_t) const { return ~0ull; }  // returns the old word
+  NT_HD NT_INLINE void dig_put(uint32_t, uint32_t) const {}
+  NT_HD NT_INLINE uint32_t dig_get(uint32_t) const { return 0; }
+  NT_HD NT_INLINE void claim_put(uint32_t) const {}
+  NT_HD NT_INLINE uint32_t claim_get() const { return 0xffffffffu; }
+  NT_HD NT_INLINE void slot_store(uint32_t, uint64_t) const {}
+  NT_HD NT_INLINE void slot_publish(uint32_t, uint64_t) const {}
+  NT_HD NT_INLINE void acquire() const {}
+  NT_HD NT_INLINE void drain_release() const {}
+  NT_HD NT_INLINE uint32_t pool_used() const { return 0; }
+  NT_HD NT_INLINE uint32_t pool_take() const { return 0; }
+  NT_HD NT_INLINE void hdr_load(uint32_t, uint32_t*, uint32_t&) const {}
+  NT_HD NT_INLINE void hdr_store(uint32_t, const uint32_t*, uint32_t) const {}
+  NT_HD NT_INLINE void tab_store(uint32_t, uint32_t, uint32_t, const ge_cached&) const {}
+  NT_HD NT_INLINE void tab_load_signed(uint32_t, uint32_t, int32_t, ge_cached&) const {}
+  NT_HD NT_INLINE void count(int) const {}
+};
+
+// a key's fingerprint in its index slot
+NT_HD NT_INLINE uint32_t ktab_fp(const uint32_t Aw[8]) { return xcache_hash(Aw, 0x94d049bbu); }
+NT_HD NT_INLINE uint64_t ktab_word(uint32_t fp, uint32_t st) { return (uint64_t)fp | ((uint64_t)st << 32); }
+
+// What a probe found: the key's fingerprint, the state and slot of its match
+// (st = 0: none) and the empty slots a first sighting may take: bit c of `ord` =
+// slot c of the emptier bucket (base pb), bit 8 + c = slot c of the other (base
+// ob); ord = 0: both buckets full -- the key stays homeless.
+struct KtProbe {
+  uint32_t fp, st, slot, pb, ob, ord;
+};
+
+// 16 relaxed slot loads (two buckets of 8: two rounds of loads in flight together)
+template <class KT>
+NT_HD NT_INLINE void ktab_probe(KtProbe& p, const uint32_t Aw[8], const KT& kt) {
+  const uint32_t mask = kt.slot_mask(), bm = mask / kKtBucket;
+  const uint32_t b0 = (xcache_hash(Aw, 0x51ed270bu) & bm) * kKtBucket;
+  const uint32_t b1 = (xcache_hash(Aw, 0x2545f491u) & bm) * kKtBucket;
+  p.fp = ktab_fp(Aw);
+  p.st = 0;
+  p.slot = 0;
+  uint64_t w[kKtCand];
+#pragma unroll
+  for (uint32_t c = 0; c < kKtCand; ++c) w[c] = kt.slot_load(((c < kKtBucket ? b0 : b1) | (c & (kKtBucket - 1))) & mask);
+  uint32_t emp = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < kKtCand; ++c) {
+    const uint32_t hi = (uint32_t)(w[c] >> 32);
+    emp |= (w[c] == 0 ? 1u : 0u) << c;
+    if (hi != 0 && (uint32_t)w[c] == p.fp && hi > p.st) {  // the furthest state wins (a key marked twice)
+      p.st = hi;
+      p.slot = ((c < kKtBucket ? b0 : b1) | (c & (kKtBucket - 1))) & mask;
+    }
+  }
+  // two-choice placement: the emptier bucket first
+  const uint32_t e0 = emp & ((1u << kKtBucket) - 1u), e1 = emp >> kKtBucket;
+  const bool second = __builtin_popcount(e1) > __builtin_popcount(e0);
+  p.pb = second ? b1 : b0;
+  p.ob = second ? b0 : b1;
+  p.ord = second ? (e1 | (e0 << kKtBucket)) : (e0 | (e1 << kKtBucket));
+}
+
+// The entry index of a ready match below the launch's capacity; kKtNoSlot otherwise.
+template <class KT>
+NT_HD NT_INLINE uint32_t ktab_ready_index(const KtProbe& p, const KT& kt) {
+  const uint32_t idx = p.st - kKtReady0;
+  return (p.st >= kKtReady0 && idx < kt.capacity()) ? idx : kKtNoSlot;
+}
+
+// The mark of a key that has no slot (p.st == 0): kKtSeen by CAS into the first slot the
+// probe saw empty.  A mark that loses its CAS to another key (a batch of new keys fills its
+// buckets at once) takes the next slot the probe saw empty, three tries in all and nothing
+// re-read; one that loses to a lane with the same key is done.
+// A mark is a partial write to a line no cache holds, acknowledged from the memory side, and
+// the wave waits for it with its next loads: a launch whose every lane marks at once queues
+// ~1.5 ns per mark behind one another (measured: 200 k marks, +0.3 ms).
+// So a key the x cache meets for the first time writes nothing here -- that sighting is
+// recorded for nothing by the x cache, which stores the key's x then -- and a key the x cache
+// has met before is claimed outright and built (ktab_take); only keys of which the x cache can
+// say nothing go through the mark (ge_frombytes_cached's `seen`).  Keys that never come back
+// never pay.
+template <class KT>
+NT_HD NT_INLINE void ktab_mark(const KtProbe& p, const KT& kt) {
+  uint32_t ord = p.ord;
+#pragma unroll 1
+  for (int a = 0; a < 3 && ord != 0; ++a) {
+    const uint32_t c = (uint32_t)__builtin_ctz(ord);
+    ord &= ord - 1u;
+    const uint32_t i = ((c < kKtBucket ? p.pb : p.ob) | (c & (kKtBucket - 1))) & kt.slot_mask();
+    const uint64_t old = kt.slot_cas(i, 0, ktab_word(p.fp, kKtSeen));
+    if (old == 0 || (uint32_t)old == p.fp) break;
+  }
+}
+// The claim of a key marked before: returns 1 for the one winner of the CAS, who builds the
+// entry after its verification (ktab_build).  A claimed or ready slot and a full pool are left
+// as they are.
+template <class KT>
+NT_HD NT_INLINE uint32_t ktab_claim(const KtProbe& p, const KT& kt) {
+  if (p.st == kKtSeen && kt.pool_used() < kt.capacity())
+    return kt.slot_cas(p.slot, ktab_word(p.fp, kKtSeen), ktab_word(p.fp, kKtClaimed)) == ktab_word(p.fp, kKtSeen) ? 1u : 0u;
+  return 0;
+}
+// A slot for a key that has none, claimed outright (the x cache vouches for an earlier
+// meeting): returns the slot won, kKtNoSlot otherwise.
+template <class KT>
+NT_HD NT_INLINE uint32_t ktab_take(const KtProbe& p, const KT& kt) {
+  if (p.st != 0) return ktab_claim(p, kt) ? p.slot : kKtNoSlot;
+  if (kt.pool_used() >= kt.capacity()) return kKtNoSlot;
+  uint32_t ord = p.ord;
+#pragma unroll 1
+  for (int a = 0; a < 3 && ord != 0; ++a) {
+    const uint32_t c = (uint32_t)__builtin_ctz(ord);
+    ord &= ord - 1u;
+    const uint32_t i = ((c < kKtBucket ? p.pb : p.ob) | (c & (kKtBucket - 1))) & kt.slot_mask();
+    const uint64_t old = kt.slot_cas(i, 0, ktab_word(p.fp, kKtClaimed));
+    if (old == 0) return i;
+    if ((uint32_t)old == p.fp) break;
+  }
+  return kKtNoSlot;
+}
+// Mark or claim in one, for a caller that has no x cache to ask.
+template <class KT>
+NT_HD NT_INLINE uint32_t ktab_sight(const KtProbe& p, const KT& kt) {
+  if (p.st == 0) {
+    ktab_mark(p, kt);
+    return 0;
+  }
+  return ktab_claim(p, kt);
+}
+// ge_frombytes_cached's `seen` for a lane parked as kKtWantMark: a key the x cache meets for
+// the first time is not marked this time
+template <class KT>
+struct KtSeenSink {
+  const KT& kt;
+  NT_HD NT_INLINE void operator()(uint32_t known) const {
+    if (KT::kEnabled && known != 1u && kt.claim_get() == kKtWantMark) kt.claim_put(known ? kKtWantTake : kKtNoSlot);
+  }
+};
+
+// ATab-shaped store adaptor of ptab_build: entries 1..8 of table t of pool entry idx
+template <class KT>
+struct KtStore {
+  const KT& kt;
+  uint32_t idx, t, on;
+  NT_HD NT_INLINE void store(uint32_t entry, const ge_cached& c) {
+    if (on && entry != 0) kt.tab_store(idx, t, entry, c);
+  }
+};
+
+// Build and publish the entries of the lanes with claim != kKtNoSlot (their keys' index slots).  Wave-uniform:
+// every lane of the row runs the arithmetic (on its own key), only the claimers
+// store.  128 doublings and three ptab_builds in a rolled loop, once per key.
+// Undecodable keys get the header alone, with the flag (the full tag makes a
+// negative entry safe); small-order keys get the flag beside their tables.
+template <class KT>
+NT_HD NT_INLINE void ktab_build(const uint32_t Aw[8], uint32_t claim, const KT& kt) {
+  const uint32_t fp = ktab_fp(Aw);
+  uint32_t idx = 0, have = 0;
+  if (claim != kKtNoSlot) {
+    idx = kt.pool_take();
+    have = idx < kt.capacity() ? 1u : 0u;
+    if (!have) kt.slot_store(claim, ktab_word(fp, kKtSeen));  // pool exhausted: seen for good
+  }
+  ge_p3 P;
+  const uint32_t ok = ge_frombytes_w(P, Aw);
+  const uint32_t flags = (ok ? 0u : kKtUndecodable) | (ge_is_small_order_affine(P) ? kKtSmallOrder : 0u);
+  KtStore<KT> st{kt, idx, 0, have & ok};
+#pragma unroll 1
+  for (uint32_t t = 0; t < kKtTables; ++t) {
+    st.t = t;
+    ptab_build(P, 0u, st, 0);
+    if (t + 1 < kKtTables) {
+      ge_p2 q;
+      ge_p3_to_p2(q, P);
+#pragma unroll 1
+      for (int r = 0; r < 63; ++r) ge_dbl_p2(q, q);
+      ge_cp c;
+      ge_dbl(c, q);
+      ge_cp_to_p3(P, c);
+    }
+  }
+  if (have) kt.hdr_store(idx, Aw, flags);
+  // every storing wave drains and releases before any slot word names its entry
+  kt.drain_release();
+  if (have) kt.slot_publish(claim, ktab_word(fp, kKtReady0 + idx));
+}
+
+// t = -[u]A - [v]R (completed) from the key's three cached tables (pool entry
+// kidx; dead: the lane has no tables, its A digits are taken as zero) and the
+// lane's own table of -R: W windows, 4 (W - 1) doublings.  Window wi adds R's digit
+// wi and, of |u|'s 64 digits, digit wi of the first 16 on A, digit 16 + wi on A',
+// digit 32 + wi of the last 32 on A'' -- so any W <= 64 is right for any valid
+// vector, (k, 1) included.  The sign of u is folded into the digit.
+// The 16 digit words (v's at 0..7, |u|'s at 8..15) wait with kt.dig_put / dig_get (the kernel:
+// LDS) and a window reads the four it needs: held in registers through this loop they are the
+// first thing the allocator spills, and it then reloads them from scratch window by window.
+template <class KT>
+NT_HD NT_INLINE int32_t kt_digit(const KT& kt, uint32_t word0, int wi) {
+  return (int32_t)(((kt.dig_get(word0 + (uint32_t)(wi >> 3)) >> (4 * (wi & 7))) & 15u) ^ 8u) - 8;
+}
+template <class ATab, class KT>
+NT_HD NT_INLINE void ladder_a3r(ge_cp& t, uint32_t uneg, int W, const ATab& at, const KT& kt, uint32_t kidx) {
+#pragma unroll 1
+  for (int wi = W - 1; wi >= 0; --wi) {
+    int j = 0;
+    if (wi == W - 1) {
+      ge_cached ce;
+      at.load_signed(kTabR, kt_digit(kt, 0, wi), ce);
+      // cached -> completed with T = Z (as ladder_ar's seed)
+      fe_sub4(t.X, ce.YpX, ce.YmX);
+      fe_carry(t.X);
+      fe_add(t.Y, ce.YpX, ce.YmX);
+      fe_carry(t.Y);
+      t.Z = ce.Z2;
+      t.T = ce.Z2;
+      j = 1;
+    } else {
+      ge_p2 acc;
+      ge_cp_to_p2(acc, t);
+#pragma unroll 1
+      for (int r = 0; r < 3; ++r) ge_dbl_p2(acc, acc);
+      ge_dbl(t, acc);
+    }
+    // additions 0: R, 1: A'' (wi < 32), 2: A', 3: A (wi < 16).  The window's four digits are
+    // taken here and packed, so that the rolled loop below indexes nothing.
+    const int nj = wi < 16 ? 4 : (wi < 32 ? 2 : 1);
+    const int wl = wi & 15;
+    const uint32_t dpack = ((uint32_t)kt_digit(kt, 0, wi) & 15u) | (((uint32_t)kt_digit(kt, 12, wi & 31) & 15u) << 4) |
+                           (((uint32_t)kt_digit(kt, 10, wl) & 15u) << 8) | (((uint32_t)kt_digit(kt, 8, wl) & 15u) << 12);
+#pragma unroll 1
+    for (; j < nj; ++j) {
+      const int32_t d = (int32_t)(((dpack >> (4 * j)) & 15u) ^ 8u) - 8;  // sign-extended nibble
+      ge_cached ce;
+      if (j == 0) {
+        at.load_signed(kTabR, d, ce);
+      } else {
+        kt.tab_load_signed(kidx, 3u - (uint32_t)j, uneg ? d : -d, ce);  // -[u]A = [|u|](u < 0 ? A : -A)
+      }
+      ge_p3 q;
+      ge_cp_to_p3(q, t);
+      ge_add_cached(t, q, ce);
+    }
+  }
+}
+
+// verify_uv for a key whose tables are cached: (u, v) any valid vector of k with
+// bit lengths <= ubits, vbits (verify_one uses sc_unbalanced's; the tests also run
+// the balanced one and (k, 1)); kflags = the entry's header flags.
+template <int MODE, class ATab, class WComb, class KT>
+NT_HD NT_INLINE uint32_t verify_uv3(const uint32_t Rw[8], const uint32_t Sw[8], const uint32_t u[8], uint32_t uneg,
+                                    const uint32_t v[8], int ubits, int vbits, uint32_t kflags, ATab& at,
+                                    const WComb& wb, const KT& kt, uint32_t kidx) {
+  const uint32_t dead = (kflags & kKtUndecodable) ? 1u : 0u;
+  uint32_t ok = sc_is_canonical(Sw) & (dead ^ 1u);
+  if (MODE == kStrict) ok &= (kflags & kKtSmallOrder) ? 0u : 1u;
+  {
+    ge_p3 R;
+    ok &= ge_frombytes_w(R, Rw);
+    if (MODE == kStrict) ok &= ge_is_small_order_affine(R) ^ 1u;
+    ptab_build(R, 1u, at, kTabR);
+  }
+  uint32_t w[8], ud[8], vd[8];
+  sc_mul(w, v, Sw);
+  sc_recode_w4(ud, u);
+  sc_recode_w4(vd, v);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    kt.dig_put((uint32_t)i, vd[i]);
+    kt.dig_put(8u + (uint32_t)i, dead ? 0u : ud[i]);
+  }
+  // 4 windows(b) >= b + 2: the signed top digit absorbs the carry
+  const int wv = (vbits + 5) >> 2, wu = ((ubits + 5) >> 2) - 32;
+  int Wn = wv > wu ? wv : wu;
+  Wn = Wn < 16 ? 16 : (Wn > 64 ? 64 : Wn);
+  const int W = wave_max(Wn);
+  ge_cp t;
+  ladder_a3r(t, uneg, W, at, kt, kidx);
+  ge_p3 acc;
+  ge_cp_to_p3(acc, t);
+  wcomb_acc(acc, w, wb);
+  return ok & fe_iszero(acc.X) & fe_eq(acc.Y, acc.Z);
+}
+
 // One verification (A, R, s encodings as words), half-size scalars:
 //   ok  <=>  s < L, A and R decode, (strict) neither is small order, and
 //            [v s mod L]B - [u]A - [v]R == identity     (= [v]([s]B - [k]A - R))
 // with (u, v) = sc_halfsize(k), k = SHA-512(R || A || M) mod L.  at holds this
 // lane's tables, wb is the wide comb of B.
+// With a key-table cache (kt): the probe comes first.  A row whose lanes ALL find a
+// finished entry carrying their key's tag takes the unbalanced vector and the
+// three-table ladder; any other row notes its sightings and runs exactly the
+// balanced code, x cache included.  What the lane owes the cache after its row -- the
+// index slot of a key it has claimed (ktab_build), or kKtWantMark for a key without a
+// slot that the x cache turns out to know -- is parked with kt.claim_put, so that no
+// word of the cache stays live across the balanced path.  live = 0: a lane that only
+// repeats another's entry (past the end of a launch) neither marks nor claims.
+template <int MODE, class ATab, class WComb, class XCache, class KT>
+NT_HD NT_INLINE uint32_t verify_one_kt(const uint32_t Aw[8], const uint32_t Rw[8], const uint32_t Sw[8],
+                                       const uint8_t* msg, uint64_t len, ATab& at, const WComb& wb, const XCache& xc,
+                                       const KT& kt, uint32_t live = 1u) {
+  uint32_t kent = 0;  // fast rows: entry index | header flags << kKtFlagShift
+  bool fast = false;
+  if (KT::kEnabled && kt.active()) {
+    KtProbe kp;
+    ktab_probe(kp, Aw, kt);
+    const uint32_t kidx = ktab_ready_index(kp, kt);
+    if (!wave_any(kidx == kKtNoSlot)) {
+      kt.acquire();  // ONE acquire between the slot loads and the first pool load
+      uint32_t tag[8], kflags, same = 1;
+      kt.hdr_load(kidx, tag, kflags);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) same &= tag[i] == Aw[i];
+      fast = !wave_any(same ^ 1u);
+      kent = kidx | (kflags << kKtFlagShift);
+    }
+    kt.claim_put(fast || !live ? kKtNoSlot : (kp.st == 0 ? kKtWantMark : (ktab_claim(kp, kt) ? kp.slot : kKtNoSlot)));
+    kt.count(fast ? kKtCntFast : kKtCntOld);
+  }
+  uint32_t k[8];
+  hram_scalar(k, Rw, Aw, msg, len);
+  uint32_t u[8], v[8], uneg;
+  if (KT::kEnabled && fast) {
+    int ub, vb;
+    sc_unbalanced(u, uneg, v, k, ub, vb);
+    return verify_uv3<MODE>(Rw, Sw, u, uneg, v, ub, vb, kent >> kKtFlagShift, at, wb, kt,
+                            kent & ((1u << kKtFlagShift) - 1u));
+  }
+  const int bits = sc_halfsize(u, uneg, v, k);
+  return verify_uv<MODE>(Aw, Rw, Sw, u, uneg, v, bits, at, wb, xc, KtSeenSink<KT>{kt});
+}
 template <int MODE, class ATab, class WComb, class XCache = NoXCache>
 NT_HD NT_INLINE uint32_t verify_one(const uint32_t Aw[8], const uint32_t Rw[8], const uint32_t Sw[8],
                                     const uint8_t* msg, uint64_t len, ATab& at, const WComb& wb,
                                     const XCache& xc = XCache()) {
-  uint32_t u[8], v[8], uneg;
-  int bits;
-  {
-    uint32_t k[8];
-    hram_scalar(k, Rw, Aw, msg, len);
-    bits = sc_halfsize(u, uneg, v, k);
-  }
-  return verify_uv<MODE>(Aw, Rw, Sw, u, uneg, v, bits, at, wb, xc);
+  return verify_one_kt<MODE>(Aw, Rw, Sw, msg, len, at, wb, xc, NoKTab());
 }
 
 // N verifications per lane in turn.  A[j] = 8 pk words, sig[j] = 16 words
 // (R || s), msg[j]/len[j] = message; at is this lane's table storage.
-template <int MODE, int N, class ATab, class WComb, class XCache = NoXCache>
+template <int MODE, int N, class ATab, class WComb, class XCache = NoXCache, class KT = NoKTab>
 NT_HD NT_INLINE void verify_n(uint32_t ok[N], const uint32_t* const A[N], const uint32_t* const sig[N],
                               const uint8_t* const msg[N], const uint64_t len[N], ATab& at, const WComb& wb,
-                              const XCache& xc = XCache()) {
+                              const XCache& xc = XCache(), const KT& kt = KT(), const uint32_t* live = nullptr) {
 #pragma unroll 1
   for (int j = 0; j < N; ++j) {
     const uint32_t* sj = pick<N>(sig, j);
@@ -673,10 +1063,30 @@ NT_HD NT_INLINE void verify_n(uint32_t ok[N], const uint32_t* const A[N], const 
     ld8(Aw, pick<N>(A, j));
     ld8(Rw, sj);
     ld8(Sw, sj + 8);
-    const uint32_t okj = verify_one<MODE>(Aw, Rw, Sw, pick<N>(msg, j), pick<N>(len, j), at, wb, xc);
+    const uint32_t okj = verify_one_kt<MODE>(Aw, Rw, Sw, pick<N>(msg, j), pick<N>(len, j), at, wb, xc, kt,
+                                               live ? pick<N>(live, j) : 1u);
 #pragma unroll
     for (int q = 0; q < N; ++q)
       if (q == j) ok[q] = okj;
+    const uint32_t owed = (KT::kEnabled && kt.active()) ? kt.claim_get() : kKtNoSlot;
+    uint32_t claim = owed >= kKtWantTake ? kKtNoSlot : owed;
+    if (KT::kEnabled && wave_any(owed == kKtWantMark || owed == kKtWantTake)) {
+      // keys without a slot that the x cache does not call new: looked up once more (nothing
+      // of the first probe was kept), then claimed outright if the x cache has met them
+      // before, marked if it cannot say
+      ld8(Aw, pick<N>(A, j));
+      KtProbe kp;
+      ktab_probe(kp, Aw, kt);
+      if (owed == kKtWantMark && kp.st == 0) ktab_mark(kp, kt);
+      if (owed == kKtWantTake) claim = ktab_take(kp, kt);
+    }
+    if (KT::kEnabled && wave_any(claim != kKtNoSlot)) {
+      // the claimers' entries, after the row's verdicts (the key is read again: nothing of it
+      // was kept across the verification)
+      kt.count(kKtCntBuild);
+      ld8(Aw, pick<N>(A, j));
+      ktab_build(Aw, claim, kt);
+    }
   }
 }
 

@@ -434,17 +434,20 @@ static int keyset_occ() {
   return occ;
 }
 int verify_occupancy() { return verify_occ(); }
+size_t ktab_entry_bytes() { return kKtEntryBytes; }
 int keyset_occupancy() { return keyset_occ(); }
 
 hipError_t launch_verify(int mode, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
                          uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
                          const uint32_t* d_combB, int bbits, void* d_ws, uint32_t ws_slots, uint64_t* d_out_words,
-                         hipStream_t s, int per_lane, XTab xt) {
+                         hipStream_t s, int per_lane, XTab xt, KTabArgs kt) {
   if (n == 0) return hipSuccess;
   if (!d_combB || !d_ws) return hipErrorInvalidValue;
+  // a key-table cache comes with a capacity (its control block holds the rest: ktab_for, context.cpp)
+  if (kt.base && (!kt.cap || kt.cap > kKtMaxEntries)) return hipErrorInvalidValue;
   const int pl = verify_per_lane_for(per_lane);
   const uint64_t blocks = verify_grid(n, ws_slots, pl);
-#define NT_V_ARGS blocks, d_pk, d_sig, d_msg, msg_bytes, d_off, d_len, n, d_combB, d_ws, d_out_words, s, pl, xt
+#define NT_V_ARGS blocks, d_pk, d_sig, d_msg, msg_bytes, d_off, d_len, n, d_combB, d_ws, d_out_words, s, pl, xt, kt
   if (bbits == kBCombBits)
     return mode == kStrict ? launch_verify_m<kStrict, kBCombBits>(NT_V_ARGS)
                            : launch_verify_m<kCofactorless, kBCombBits>(NT_V_ARGS);

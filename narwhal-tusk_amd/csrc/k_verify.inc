@@ -13,12 +13,16 @@ namespace nt {
 // after the other): the host entry points' last chunk, whose kernel is all
 // that is left after the last PCIe copy (DESIGN.md §6.4).
 // --------------------------------------------------------------------------
-template <int MODE, int OCC, int WB, int NPER>
+// KTAB: the variant that carries the key-table cache (DevKTab).  A launch without a cache
+// (none allocated, NT_KTAB_KEYS=0, or an occupancy other than the default's) runs the KTAB =
+// false variant, whose code is the kernel's as it was before the cache: nothing of the cache is
+// compiled beside its balanced path.
+template <int MODE, int OCC, int WB, int NPER, bool KTAB>
 __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify(
     const uint32_t* __restrict__ pk, const uint32_t* __restrict__ sig, const uint8_t* __restrict__ msg,
     uint64_t msg_bytes, const uint64_t* __restrict__ off, const uint64_t* __restrict__ len, uint64_t n,
     const uint32_t* __restrict__ combB, uint4* __restrict__ ws, unsigned long long* __restrict__ out_bits,
-    uint4* xtab, uint32_t xmask) {
+    uint4* xtab, uint32_t xmask, uint32_t* kbase, uint32_t kcap) {
   WsATab at{ws, blockIdx.x};
   const WideComb<WB> wb{combB};
   const DevXCache xc{xtab, xmask};
@@ -43,7 +47,13 @@ __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify(
       L[j] = ms.len;
     }
     uint32_t ok[NPER];
-    verify_n<MODE, NPER>(ok, A, S, M, L, at, wb, xc);
+    if constexpr (KTAB) {
+      const DevKTab kt{kbase, kcap};
+      // act: lanes past n (they repeat entry n - 1) and lanes with a bad slice leave the cache alone
+      verify_n<MODE, NPER>(ok, A, S, M, L, at, wb, xc, kt, act);
+    } else {
+      verify_n<MODE, NPER>(ok, A, S, M, L, at, wb, xc);
+    }
 #pragma unroll
     for (int j = 0; j < NPER; ++j) {
       const unsigned long long bal = __ballot(ok[j] & act[j]);
@@ -59,22 +69,28 @@ template <int MODE, int WB>
 hipError_t launch_verify_m(uint64_t blocks, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
                            uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
                            const uint32_t* d_combB, void* d_ws, uint64_t* d_out_words, hipStream_t s, int per_lane,
-                           XTab xt) {
+                           XTab xt, KTabArgs kt) {
   const int occ = verify_occupancy();
-#define NT_V_LAUNCH(O, P)                                                                                  \
-  hipLaunchKernelGGL((k_ed25519_verify<MODE, O, WB, P>), dim3((uint32_t)blocks), dim3(kBlock), 0, s,          \
+#define NT_V_LAUNCH(O, P) NT_V_LAUNCH_K(O, P, false)
+#define NT_V_LAUNCH_K(O, P, K)                                                                             \
+  hipLaunchKernelGGL((k_ed25519_verify<MODE, O, WB, P, K>), dim3((uint32_t)blocks), dim3(kBlock), 0, s,       \
                      (const uint32_t*)d_pk, (const uint32_t*)d_sig, d_msg, msg_bytes, d_off, d_len, n, d_combB, \
-                     (uint4*)d_ws, (unsigned long long*)d_out_words, (uint4*)xt.tab, xt.mask)
+                     (uint4*)d_ws, (unsigned long long*)d_out_words, (uint4*)xt.tab, xt.mask,                   \
+                     (uint32_t*)kt.base, kt.cap)
   if (per_lane == 1 && kVPer != 1) {
     if (occ != 2) return hipErrorInvalidValue;  // verify_per_lane_for() never asks for it
-    NT_V_LAUNCH(2, 1);
+    if (kt.base) NT_V_LAUNCH_K(2, 1, true);
+    else NT_V_LAUNCH(2, 1);
   } else if (occ == 1) {
     NT_V_LAUNCH(1, kVPer);
   } else if (occ == 3) {
     NT_V_LAUNCH(3, kVPer);
+  } else if (kt.base) {
+    NT_V_LAUNCH_K(2, kVPer, true);
   } else {
     NT_V_LAUNCH(2, kVPer);
   }
+#undef NT_V_LAUNCH_K
 #undef NT_V_LAUNCH
   return hipGetLastError();
 }

@@ -5,5 +5,5 @@
 namespace nt {
 template hipError_t launch_verify_m<kStrict, kBCombBits>(uint64_t, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t,
                                               const uint64_t*, const uint64_t*, uint64_t, const uint32_t*, void*,
-                                              uint64_t*, hipStream_t, int, XTab);
+                                              uint64_t*, hipStream_t, int, XTab, KTabArgs);
 }  // namespace nt

@@ -225,6 +225,130 @@ struct DevXCache {
   }
 };
 
+// The key-table cache of the verify kernel (ed25519_ops.hpp KTab) in global memory, one per
+// device entry, read and written by launches on any stream with no ordering between them.
+// Shared words (index slots, control block) are only ever touched by agent-scope atomics; pool
+// entries by plain VECTOR accesses (per-lane addresses through a non-restrict pointer: never the
+// scalar path) -- stored before the builder's drain + agent-scope release + slot store,
+// loaded after the reader's slot loads + ONE agent-scope acquire.  Insert-only: a pool line is
+// never read before a slot names its entry and never written after, and entries are 128-byte
+// aligned multiples of 128 bytes, so no cache line a reader may hold goes stale.
+// Indices: slots are masked here, entry indices are checked against cap by the callers
+// (ktab_ready_index, ktab_build) before they get here, table and point numbers are clamped here.
+struct DevKTab {
+  static constexpr bool kEnabled = true;
+  static constexpr uint32_t kEntryQuads = kKtEntryBytes / 16, kHeaderQuads = kKtHeaderBytes / 16;
+  static_assert(kKtEntryBytes % 128 == 0 && kKtPointBytes == 160, "entry = whole 128-byte lines of 10-quad points");
+  // One pointer and the launch's capacity are all a launch carries in registers.  base: the
+  // control block (128 bytes: words 0..3 = entries handed out and the three row counters,
+  // words 4..5 = the pool's address, word 6 = slots - 1; the last three written once, before the
+  // first launch, and read here through the scalar path: they are never handed off), then the
+  // index slots.
+  uint32_t* base;
+  uint32_t cap;
+  NT_D NT_INLINE bool active() const { return base != nullptr; }
+  NT_D NT_INLINE uint32_t slot_mask() const { return base[6]; }
+  NT_D NT_INLINE uint32_t capacity() const { return cap; }
+  NT_D NT_INLINE unsigned long long* slot_ptr(uint32_t i) const {
+    return (unsigned long long*)(base + 32) + (i & slot_mask());
+  }
+  NT_D NT_INLINE uint4* pool_ptr() const { return (uint4*)(*(const unsigned long long*)(base + 4)); }
+  NT_D NT_INLINE uint32_t* ctl_ptr() const { return base; }
+  NT_D NT_INLINE uint64_t slot_load(uint32_t i) const {
+    return __hip_atomic_load(slot_ptr(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // returns the word found (== expect: the exchange happened)
+  NT_D NT_INLINE uint64_t slot_cas(uint32_t i, uint64_t expect, uint64_t desired) const {
+    unsigned long long e = expect;
+    (void)__hip_atomic_compare_exchange_strong(slot_ptr(i), &e, (unsigned long long)desired, __ATOMIC_RELAXED,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return e;
+  }
+  // a lane's claimed slot while its balanced verification runs: LDS, not a register
+  NT_D NT_INLINE uint32_t* claim_cell() const {
+    __shared__ uint32_t s_claim[kBlock];
+    return s_claim + threadIdx.x;
+  }
+  // the three-table ladder's 16 digit words, [word][thread]
+  NT_D NT_INLINE uint32_t* dig_cell(uint32_t i) const {
+    __shared__ uint32_t s_dig[16 * kBlock];
+    return s_dig + (i & 15u) * kBlock + threadIdx.x;
+  }
+  NT_D NT_INLINE void dig_put(uint32_t i, uint32_t w) const { *dig_cell(i) = w; }
+  NT_D NT_INLINE uint32_t dig_get(uint32_t i) const { return *dig_cell(i); }
+  NT_D NT_INLINE void claim_put(uint32_t v) const { *claim_cell() = v; }
+  NT_D NT_INLINE uint32_t claim_get() const { return *claim_cell(); }
+  NT_D NT_INLINE void slot_store(uint32_t i, uint64_t w) const {
+    __hip_atomic_store(slot_ptr(i), (unsigned long long)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // after drain_release(): the store that names a finished entry
+  NT_D NT_INLINE void slot_publish(uint32_t i, uint64_t w) const { slot_store(i, w); }
+  NT_D NT_INLINE void acquire() const { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+  // the storing wave: its vector stores drained, then the agent-scope release, then a drain of
+  // the release's own write-back -- all before the slot store that follows
+  NT_D NT_INLINE void drain_release() const {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  NT_D NT_INLINE uint32_t pool_used() const { return __hip_atomic_load(ctl_ptr(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  NT_D NT_INLINE uint32_t pool_take() const {
+    return __hip_atomic_fetch_add(ctl_ptr(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // once per wave row, by one lane
+  NT_D NT_INLINE void count(int which) const {
+    if ((threadIdx.x & 63u) == 0) __hip_atomic_fetch_add(ctl_ptr() + 1 + which, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  NT_D NT_INLINE uint4* entry(uint32_t idx) const { return pool_ptr() + (size_t)idx * kEntryQuads; }
+  NT_D NT_INLINE uint4* point(uint32_t idx, uint32_t t, uint32_t j) const {
+    return entry(idx) + kHeaderQuads + ((t % kKtTables) * kKtPerTable + ((j - 1u) & (kKtPerTable - 1u))) * 10u;
+  }
+  NT_D NT_INLINE void hdr_load(uint32_t idx, uint32_t tag[8], uint32_t& flags) const {
+    const uint4* e = entry(idx);
+    const uint4 a = e[0], b = e[1], c = e[2];
+    tag[0] = a.x; tag[1] = a.y; tag[2] = a.z; tag[3] = a.w; tag[4] = b.x; tag[5] = b.y; tag[6] = b.z; tag[7] = b.w;
+    flags = c.x;
+  }
+  NT_D NT_INLINE void hdr_store(uint32_t idx, const uint32_t tag[8], uint32_t flags) const {
+    uint4* e = entry(idx);
+    e[0] = make_uint4(tag[0], tag[1], tag[2], tag[3]);
+    e[1] = make_uint4(tag[4], tag[5], tag[6], tag[7]);
+    e[2] = make_uint4(flags, 0u, 0u, 0u);
+  }
+  NT_D NT_INLINE void tab_store(uint32_t idx, uint32_t t, uint32_t j, const ge_cached& c) const {
+    uint32_t w[40];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+      w[i] = c.YpX.v[i]; w[10 + i] = c.YmX.v[i]; w[20 + i] = c.Z2.v[i]; w[30 + i] = c.T2d.v[i];
+    }
+    uint4* p = point(idx, t, j);
+#pragma unroll
+    for (int q = 0; q < 10; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  }
+  // point |d| of table t with the sign of d; d = 0: the identity, synthesized (the load still
+  // goes to a valid point of the entry and is dropped)
+  NT_D NT_INLINE void tab_load_signed(uint32_t idx, uint32_t t, int32_t d, ge_cached& c) const {
+    const uint32_t a = (uint32_t)(d < 0 ? -d : d);
+    const uint4* p = point(idx, t, a);
+    uint32_t w[40];
+#pragma unroll
+    for (int q = 0; q < 10; ++q) {
+      const uint4 v = p[q];
+      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    }
+    ge_cached z;
+    ge_cached_0(z);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+      c.YpX.v[i] = a ? w[i] : z.YpX.v[i];
+      c.YmX.v[i] = a ? w[10 + i] : z.YmX.v[i];
+      c.Z2.v[i] = a ? w[20 + i] : z.Z2.v[i];
+      c.T2d.v[i] = a ? w[30 + i] : z.T2d.v[i];
+    }
+    ge_cached_cneg(c, d < 0);
+  }
+};
+
 // ---- key-cache verification: up to 64 signatures per lane, one inversion ----
 #ifndef NT_KS_PER_LANE
 #define NT_KS_PER_LANE 64
@@ -328,7 +452,7 @@ template <int MODE, int WB>
 hipError_t launch_verify_m(uint64_t blocks, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
                            uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
                            const uint32_t* d_combB, void* d_ws, uint64_t* d_out_words, hipStream_t s, int per_lane,
-                           XTab xt);
+                           XTab xt, KTabArgs kt);
 template <int MODE, int WA, int WB>
 hipError_t launch_keyset_m(const KsPlan& plan, const uint32_t* d_key_idx, const uint8_t* d_sig, const uint8_t* d_msg,
                            uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n, const uint32_t* d_meta,

@@ -215,6 +215,16 @@ struct Device {
   uint64_t xtab_reserved = 0;   // (entry) its bytes in the budget
   bool xtab_tried = false;      // (entry) under tables_mu
   std::atomic<int> xtab_ready{0};  // this slot's d_xtab / xslots are set
+  // The key-table cache (ed25519_ops.hpp KTab): one per device entry, shared like the x cache;
+  // ktab_for() (context.cpp) allocates it with the first verify -- the control block and the
+  // index zero-filled, the pool as hipMalloc leaves it (a pool line is read only after a slot
+  // names its entry) -- and never rewrites or frees an entry before the context closes.
+  void* d_kslots = nullptr;     // the control block, then nt::kKTabIndexSlots slots of 8 bytes (nt::KTabArgs::base)
+  void* d_kpool = nullptr;      // kcap entries of nt::ktab_entry_bytes()
+  uint32_t kcap = 0;
+  uint64_t ktab_reserved = 0;   // (entry) its bytes in the budget
+  bool ktab_tried = false;      // (entry) under tables_mu
+  std::atomic<int> ktab_ready{0};  // this slot's d_kslots / d_kpool / kcap are set
   uint32_t ws_slots = 0;
   uint32_t sign_blocks = 0;
   uint32_t cus = 0;
@@ -249,12 +259,15 @@ struct Device {
   ~Device() {
     if (comb_reserved && budget) budget->release(comb_reserved);
     if (xtab_reserved && budget) budget->release_aux(xtab_reserved);
+    if (ktab_reserved && budget) budget->release_aux(ktab_reserved);
     if (ordinal < 0) return;
     (void)hipSetDevice(ordinal);
     for (Lane& l : lane)
       if (l.stream) (void)hipStreamSynchronize(l.stream);
     extra.clear();
     if (entry == this && d_xtab) (void)hipFree(d_xtab);
+    if (entry == this && d_kslots) (void)hipFree(d_kslots);
+    if (entry == this && d_kpool) (void)hipFree(d_kpool);
     for (hipEvent_t e : {lane[0].ws_done, lane[0].stash_done, lane[1].ws_done, lane[1].stash_done})
       if (e) (void)hipEventDestroy(e);
     for (auto& e : cev)
@@ -353,6 +366,21 @@ struct Device {
     return xt;
   }
 
+  // The key-table cache as a launch sees it.  NT_KTAB_KEYS is read again at every launch: 0 = no
+  // cache for this launch, a value below the allocated capacity confines the launch to the pool's
+  // first entries (entries beyond it are misses, none is added), a larger one changes nothing.
+  nt::KTabArgs ktab() const {
+    nt::KTabArgs kt;
+    if (!d_kslots || !d_kpool) return kt;
+    uint32_t cap = kcap;
+    if (const char* e = std::getenv("NT_KTAB_KEYS")) cap = (uint32_t)std::min<unsigned long long>(std::strtoull(e, nullptr, 10), kcap);
+    if (cap) {
+      kt.base = d_kslots;
+      kt.cap = cap;
+    }
+    return kt;
+  }
+
   // compute stream of chunk c
   hipStream_t cstr(int c) const { return lane[c & 1].stream; }
 
@@ -375,7 +403,7 @@ struct Device {
     NT_CHK0(grow_synced(l.ws, nt::ws_bytes_per_slot() * slots, l.ws_done));
     if (hipStreamWaitEvent(s, l.ws_done, 0) != hipSuccess ||
         nt::launch_verify(mode, pk, sig, msg, msg_bytes, off, len, n, d_combB, bbits, l.ws.p, (uint32_t)slots, out, s,
-                          per_lane, xtab()) != hipSuccess ||
+                          per_lane, xtab(), ktab()) != hipSuccess ||
         hipEventRecord(l.ws_done, s) != hipSuccess)
       return NT_EHIP;
     return NT_OK;

@@ -249,7 +249,13 @@ NT_HD NT_INLINE uint32_t lat_quot(double d0, double d1) {
 }
 
 constexpr int kLatMaxSteps = 600;
-constexpr double kLatStop = 0x1.6a09e667f3bcdp+127;  // 2^127.5
+// The remainder bound the sequence stops at, as floor(log2): 2^(S + 0.5).
+//   kLatBalanced   2^127.5: |u|, v ~ 2^128 (sc_halfsize, every key)
+//   kLatUnbalanced 2^191.5: |u| ~ 2^192, v ~ 2^64 (sc_unbalanced: keys whose [2^64]A, [2^128]A
+//                           are at hand, verify_uv3) -- about half the Euclid steps
+constexpr int kLatBalanced = 127, kLatUnbalanced = 191;
+// 2^(S + 0.5)
+NT_HD NT_INLINE double lat_stop(int S) { return ldexp(0x1.6a09e667f3bcdp+0, S); }
 
 // n-word helpers of the Lehmer batches
 // out[0..N] = a * m
@@ -335,17 +341,19 @@ NT_HD NT_INLINE void lat_exact_step(LatState& S) {
 // bound and b - r exceeds the bound of both rows: then the exact remainders stay
 // positive and ordered, i.e. every accepted quotient IS the exact Euclid
 // quotient and the batch lands on the same remainder pair the one-step loop
-// visits.  Steps stop above 2^132 (the one-step loop finishes the last few).
+// visits.  Steps stop above 2^(S + 5) = 2^132 for the balanced stop S = 127 (the
+// one-step loop finishes the last few).
 // The applied state is re-validated (r0' > r1' >= 0, |t| in 4 words); an
 // empty or invalid batch falls back to one exact step.
-constexpr double kLehmerStop = 0x1p136;  // batches while r1 >= 2^136
-constexpr int kLehmerMaxInner = 48;      // > the 37 all-ones quotients of 26 bits
-NT_HD NT_INLINE void lat_lehmer_batch(LatState& S) {
+constexpr int kLehmerStopOver = 9;   // batches while r1 >= 2^(S + 9) = 2^136 (balanced)
+constexpr int kLehmerThrOver = 5;    // no batched remainder below 2^(S + 5)
+constexpr int kLehmerMaxInner = 48;  // > the 37 all-ones quotients of 26 bits
+NT_HD NT_INLINE void lat_lehmer_batch(LatState& S, int stop) {
   int e;
   frexp(S.d0, &e);
   const int sh = e - 53;  // d0 in [2^(e-1), 2^e): d0 / 2^sh is an integer in [2^52, 2^53)
   double a = ldexp(S.d0, -sh), b = floor(ldexp(S.d1, -sh));
-  const double thr = ldexp(1.0, 132 - sh);
+  const double thr = ldexp(1.0, stop + kLehmerThrOver - sh);
   double x0 = 1.0, y0 = 0.0, x1 = 0.0, y1 = 1.0;
   int n = 0;
 #pragma unroll 1
@@ -433,9 +441,15 @@ NT_HD NT_INLINE void lat_lehmer_batch(LatState& S) {
 }
 
 // LEHMER = false: the one-step loop only (the reference the tests compare the
-// batched reduction with; the kernels use LEHMER = true).
-template <bool LEHMER>
-NT_HD NT_INLINE int sc_halfsize_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8]) {
+// batched reduction with; the kernels use LEHMER = true).  STOP: kLatBalanced or
+// kLatUnbalanced.  ubits / vbits: bit lengths of |u| and v (never underestimates).
+// With the unbalanced stop the odd-v fix-up picks the neighbour that costs the
+// three-table ladder fewer windows: max(bitlen |u| - 128, bitlen v).
+template <bool LEHMER, int STOP>
+NT_HD NT_INLINE void sc_lattice_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8], int& ubits,
+                                  int& vbits) {
+  static_assert(STOP == kLatBalanced || STOP == kLatUnbalanced, "remainder bound");
+  constexpr int kSkew = 2 * (STOP - kLatBalanced);  // bits of |u| that cost nothing
   LatState S;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -450,12 +464,14 @@ NT_HD NT_INLINE int sc_halfsize_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], 
   S.d1 = bn_to_f64<8>(S.r1);
   S.steps = 0;
   if (LEHMER) {
+    const double lstop = ldexp(1.0, STOP + kLehmerStopOver);
 #pragma unroll 1
-    while (S.d1 >= kLehmerStop && S.steps < kLatMaxSteps) lat_lehmer_batch(S);
+    while (S.d1 >= lstop && S.steps < kLatMaxSteps) lat_lehmer_batch(S, STOP);
   }
-  // Inside the loop r1 >= 2^127.5, so |t0|, |t1| <= 8L / r1 < 2^128: 4 words.
+  // Inside the loop r1 >= 2^(STOP + 0.5), so |t0|, |t1| <= 8L / r1 < 2^128: 4 words.
+  const double stop = lat_stop(STOP);
 #pragma unroll 1
-  while (S.d1 >= kLatStop && S.steps < kLatMaxSteps) lat_exact_step(S);
+  while (S.d1 >= stop && S.steps < kLatMaxSteps) lat_exact_step(S);
   uint32_t(&r0)[8] = S.r0;
   uint32_t(&r1)[8] = S.r1;
   uint32_t(&t0)[4] = S.t0;
@@ -463,7 +479,6 @@ NT_HD NT_INLINE int sc_halfsize_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], 
   const uint32_t t1neg = S.t1neg;
   const double d0 = S.d0, d1 = S.d1;
   const int steps = S.steps;
-  int bits;
   if (t1[0] & 1u) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -471,9 +486,8 @@ NT_HD NT_INLINE int sc_halfsize_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], 
       v[i] = i < 4 ? t1[i] : 0u;
     }
     uneg = t1neg;
-    bits = f64_bitlen(d1);
-    const int bt = f64_bitlen(bn_to_f64<4>(t1));
-    bits = bt > bits ? bt : bits;
+    ubits = f64_bitlen(d1);
+    vbits = f64_bitlen(bn_to_f64<4>(t1));
   } else {
     // t1 even => t0 odd (gcd(t0, t1) = 1).  Candidates with the sign of t0:
     // b0 = (r0, t0) and b2 = b0 - q b1 = (r0 - q r1, |t0| + q |t1|).
@@ -489,8 +503,8 @@ NT_HD NT_INLINE int sc_halfsize_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], 
     bn_addmul1<8>(t2, t1w, q);
     const int b0r = f64_bitlen(d0), b0t = f64_bitlen(bn_to_f64<4>(t0));
     const int b2r = f64_bitlen(bn_to_f64<8>(r2)), b2t = f64_bitlen(bn_to_f64<8>(t2));
-    const int c0 = b0r > b0t ? b0r : b0t;
-    const int c2 = b2r > b2t ? b2r : b2t;
+    const int c0 = b0r - kSkew > b0t ? b0r - kSkew : b0t;
+    const int c2 = b2r - kSkew > b2t ? b2r - kSkew : b2t;
     const bool use2 = d1 > 0.0 && c2 < c0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -498,9 +512,10 @@ NT_HD NT_INLINE int sc_halfsize_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], 
       v[i] = use2 ? t2[i] : (i < 4 ? t0[i] : 0u);
     }
     uneg = t1neg ^ 1u;
-    bits = use2 ? c2 : c0;
+    ubits = use2 ? b2r : b0r;
+    vbits = use2 ? b2t : b0t;
   }
-  if (steps >= kLatMaxSteps || bits > 250) {
+  if (steps >= kLatMaxSteps || ubits > 250 || vbits > 250) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       u[i] = k[i];
@@ -508,9 +523,30 @@ NT_HD NT_INLINE int sc_halfsize_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], 
     }
     v[0] = 1;
     uneg = 0;
-    bits = 253;
+    ubits = 253;
+    vbits = 1;
   }
-  return bits;
+}
+// The balanced vector; returns max(bitlen |u|, bitlen v).
+template <bool LEHMER>
+NT_HD NT_INLINE int sc_halfsize_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8]) {
+  int ub, vb;
+  sc_lattice_t<LEHMER, kLatBalanced>(u, uneg, v, k, ub, vb);
+  return ub > vb ? ub : vb;
+}
+// The unbalanced vector of verify_uv3: |u| ~ 2^192, v ~ 2^64.
+template <bool LEHMER>
+NT_HD NT_INLINE void sc_unbalanced_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8], int& ubits,
+                                     int& vbits) {
+  sc_lattice_t<LEHMER, kLatUnbalanced>(u, uneg, v, k, ubits, vbits);
+}
+NT_HD NT_INLINE void sc_unbalanced(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8], int& ubits,
+                                   int& vbits) {
+#ifdef NT_LAT_ONE_STEP  // A/B builds only
+  sc_unbalanced_t<false>(u, uneg, v, k, ubits, vbits);
+#else
+  sc_unbalanced_t<true>(u, uneg, v, k, ubits, vbits);
+#endif
 }
 NT_HD NT_INLINE int sc_halfsize(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8]) {
 #ifdef NT_LAT_ONE_STEP  // A/B builds only

@@ -26,6 +26,8 @@ _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 
+NT_INFO_KTAB = 0x10000
+
 EXPORTED = [
     "nt_init", "nt_init_device", "nt_init_devices", "nt_free", "nt_num_devices", "nt_strerror", "nt_version",
     "nt_sha512_trunc32", "nt_ed25519_verify_strict", "nt_ed25519_verify_batch_groups",
@@ -255,6 +257,16 @@ class Backend:
         out = np.zeros(8, np.uint64)
         _check(self.lib.nt_memory_info(self.ctx, int(dev), _p(out, _u64p)), "nt_memory_info")
         return dict(zip(MEMORY_INFO_KEYS, (int(x) for x in out)))
+
+    def ktab_info(self, dev=0):
+        """The verify kernel's key-table cache on device entry `dev` (nt_memory_info with NT_INFO_KTAB; a
+        library older than the cache refuses it), once the launches
+        of interest have completed: entries used, capacity, bytes, and the wave rows that took the
+        short ladder / built entries / ran the balanced path."""
+        out = np.zeros(8, np.uint64)
+        _check(self.lib.nt_memory_info(self.ctx, int(dev) | NT_INFO_KTAB, _p(out, _u64p)), "nt_memory_info")
+        keys = ("used", "capacity", "bytes", "fast_rows", "builds", "old_rows", "index_slots")
+        return dict(zip(keys, (int(x) for x in out)))
 
     def dev_stream(self, dev=0, which=0):
         """Raw hipStream_t of device entry `dev`'s compute stream `which` (0 / 1):
