@@ -958,6 +958,29 @@ NT_HD NT_INLINE void ladder_a3r(ge_cp& t, uint32_t uneg, int W, const ATab& at, 
   }
 }
 
+// verify_uv3's variable-base part, t = -[u]A - [v]R (completed): the digits of |u| and v
+// parked for ladder_a3r (dead: the key has no tables, its digits are zero), the window count
+// of the vector's bit lengths -- every lane of a wave runs its wave's largest -- and the ladder.
+// at holds the lane's table of -R already.
+template <class ATab, class KT>
+NT_HD NT_INLINE void ladder_uv3(ge_cp& t, const uint32_t u[8], uint32_t uneg, const uint32_t v[8], int ubits,
+                                int vbits, uint32_t dead, const ATab& at, const KT& kt, uint32_t kidx) {
+  uint32_t ud[8], vd[8];
+  sc_recode_w4(ud, u);
+  sc_recode_w4(vd, v);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    kt.dig_put((uint32_t)i, vd[i]);
+    kt.dig_put(8u + (uint32_t)i, dead ? 0u : ud[i]);
+  }
+  // 4 windows(b) >= b + 2: the signed top digit absorbs the carry
+  const int wv = (vbits + 5) >> 2, wu = ((ubits + 5) >> 2) - 32;
+  int Wn = wv > wu ? wv : wu;
+  Wn = Wn < 16 ? 16 : (Wn > 64 ? 64 : Wn);
+  const int W = wave_max(Wn);
+  ladder_a3r(t, uneg, W, at, kt, kidx);
+}
+
 // verify_uv for a key whose tables are cached: (u, v) any valid vector of k with
 // bit lengths <= ubits, vbits (verify_one uses sc_unbalanced's; the tests also run
 // the balanced one and (k, 1)); kflags = the entry's header flags.
@@ -974,22 +997,10 @@ NT_HD NT_INLINE uint32_t verify_uv3(const uint32_t Rw[8], const uint32_t Sw[8], 
     if (MODE == kStrict) ok &= ge_is_small_order_affine(R) ^ 1u;
     ptab_build(R, 1u, at, kTabR);
   }
-  uint32_t w[8], ud[8], vd[8];
+  uint32_t w[8];
   sc_mul(w, v, Sw);
-  sc_recode_w4(ud, u);
-  sc_recode_w4(vd, v);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    kt.dig_put((uint32_t)i, vd[i]);
-    kt.dig_put(8u + (uint32_t)i, dead ? 0u : ud[i]);
-  }
-  // 4 windows(b) >= b + 2: the signed top digit absorbs the carry
-  const int wv = (vbits + 5) >> 2, wu = ((ubits + 5) >> 2) - 32;
-  int Wn = wv > wu ? wv : wu;
-  Wn = Wn < 16 ? 16 : (Wn > 64 ? 64 : Wn);
-  const int W = wave_max(Wn);
   ge_cp t;
-  ladder_a3r(t, uneg, W, at, kt, kidx);
+  ladder_uv3(t, u, uneg, v, ubits, vbits, dead, at, kt, kidx);
   ge_p3 acc;
   ge_cp_to_p3(acc, t);
   wcomb_acc(acc, w, wb);

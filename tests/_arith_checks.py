@@ -89,7 +89,21 @@ def _p(a):
 
 ENTRIES = ["fe_mul", "fe_sq", "fe_sq_wide", "fe_carry", "fe_tobytes", "fe_frombytes", "fe_invert", "sc_reduce512",
            "sc_muladd", "sc_mul", "sc_reduce_half", "sc_recode_w4", "sc_is_canonical", "sc_halfsize", "hram",
-           "point_checks", "ladder_uv"]
+           "point_checks", "ladder_uv", "sc_unbalanced", "ktab_fill", "ktab_point", "ladder_uv3"]
+
+# the probe's key table (tests/cpp/nt_probe_items.hpp, laid out as kernels_common.hpp DevKTab reads it):
+# a 128-byte control block (word 0: entries handed out), KT_SLOTS index slots of 8 bytes
+# {fingerprint, state}, then `capacity` pool entries of KT_ENTRY_BYTES (a 128-byte header: 8 tag
+# words, the flags; 3 tables of 8 cached points of 40 words)
+KT_SLOTS, KT_CTL_BYTES, KT_ENTRY_BYTES, KT_HEADER_BYTES, KT_POINT_BYTES = 4096, 128, 3968, 128, 160
+KT_POOL_OFF = KT_CTL_BYTES + 8 * KT_SLOTS
+KT_SEEN, KT_CLAIMED, KT_READY0, KT_NO_SLOT = 1, 2, 16, 0xffffffff
+KT_UNDECODABLE, KT_SMALL_ORDER = 1, 2
+
+
+def ktab_blob(capacity):
+    """an empty key table of `capacity` entries"""
+    return np.zeros(KT_POOL_OFF + capacity * KT_ENTRY_BYTES, np.uint8)
 
 
 class Runner:
@@ -216,6 +230,46 @@ class Runner:
         bits = np.array([x[2] for x in uvb], np.int32)
         out = np.zeros((len(uvb), 8), np.uint32)
         self._call("ladder_uv", len(uvb), _p(a), _p(r), _p(u), _p(neg), _p(v), _p(bits), _p(out))
+        raw = out.tobytes()
+        return [raw[i:i + 32] for i in range(0, len(raw), 32)]
+
+    def sc_unbalanced(self, ks, lehmer):
+        """(u signed, v, ubits, vbits) per scalar from sc_unbalanced_t<lehmer>"""
+        a = _words(ks)
+        n = len(a)
+        u, v = np.zeros((n, 8), np.uint32), np.zeros((n, 8), np.uint32)
+        neg, ub, vb = np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._call("sc_unbalanced", n, _p(a), _p(u), _p(neg), _p(v), _p(ub), _p(vb), ctypes.c_int(int(lehmer)))
+        return [(-uu if ng else uu, vv, int(x), int(y)) for uu, ng, vv, x, y in zip(_ints(u), neg, _ints(v), ub, vb)]
+
+    def ktab_fill(self, keys, blob, capacity):
+        """builds the table of each key (probe, take, build) in `blob`; the index slot each item won, or KT_NO_SLOT"""
+        a = np.frombuffer(b"".join(keys), np.uint32).copy()
+        slot = np.zeros(len(keys), np.uint32)
+        self._call("ktab_fill", len(keys), _p(a), _p(blob), ctypes.c_uint32(capacity), _p(slot))
+        return [int(x) for x in slot]
+
+    def ktab_point(self, keys, tds, blob, capacity):
+        """(entry index or KT_NO_SLOT, tag match, header flags, encoding of the cached point
+        tab_load_signed(index, t, d)) per (key, (t, d))"""
+        a = np.frombuffer(b"".join(keys), np.uint32).copy()
+        td = np.array(tds, np.int32).reshape(len(keys), 2)
+        out3, enc = np.zeros((len(keys), 3), np.uint32), np.zeros((len(keys), 8), np.uint32)
+        self._call("ktab_point", len(keys), _p(a), _p(td), _p(blob), ctypes.c_uint32(capacity), _p(out3), _p(enc))
+        raw = enc.tobytes()
+        return [(int(o[0]), int(o[1]), int(o[2]), raw[32 * i:32 * i + 32]) for i, o in enumerate(out3)]
+
+    def ladder_uv3(self, kidx, Rs, vecs, blob, capacity):
+        """encoding of -[u]A - [v]R per item through the cached tables of pool entry kidx;
+        vecs = (u signed, v, ubits, vbits, dead) per item"""
+        ki = np.array(kidx, np.uint32)
+        r = np.frombuffer(b"".join(Rs), np.uint32).copy()
+        u = _words([abs(x[0]) for x in vecs])
+        v = _words([x[1] for x in vecs])
+        sc = np.array([[1 if x[0] < 0 else 0, x[2], x[3], x[4]] for x in vecs], np.uint32)
+        out = np.zeros((len(vecs), 8), np.uint32)
+        self._call("ladder_uv3", len(vecs), _p(ki), _p(r), _p(u), _p(v), _p(sc), _p(blob), ctypes.c_uint32(capacity),
+                   _p(out))
         raw = out.tobytes()
         return [raw[i:i + 32] for i in range(0, len(raw), 32)]
 
@@ -578,3 +632,372 @@ def check_ladder(run, halfsize):
     got = run.ladder_uv(As, Rs, uvb)
     for i, (g, w) in enumerate(zip(got, want)):
         assert g == w, (run.name, "wave", i // 64, "lane", i % 64, uvb[i])
+
+
+# --------------------------------------------------------------------------
+# the unbalanced lattice vector (sc_unbalanced: the remainder sequence stopped at 2^191.5)
+# --------------------------------------------------------------------------
+L8 = 8 * L
+ISQRT = __import__("math").isqrt
+STOP_U = ISQRT(1 << 383)  # floor(2^191.5): sc25519.hpp lat_stop(kLatUnbalanced)
+
+
+def _euclid(k):
+    """(dividend, divisor, quotient) of every step of Euclid on (8L, k)"""
+    r0, r1 = L8, k
+    while r1:
+        q = r0 // r1
+        yield r0, r1, q
+        r0, r1 = r1, r0 - q * r1
+
+
+@functools.lru_cache(maxsize=None)
+def unbalanced_quotient_scalars():
+    """k = floor(8L p / q) +- (2^e + j): the continued fraction of k / 8L follows p / q down to a
+    remainder of about 8L / q = 2^(255 - qb), where the perturbation leaves a partial quotient of
+    about 2^(255 - 2 qb - e): 2^40, 2^30, 2^20 and (e = 0) 2^125 .. 2^155 with dividends across the
+    final stop (2^191.5), the batch threshold (2^196) and the Lehmer stop (2^200)"""
+    rng = random.Random(191)
+    gcd = __import__("math").gcd
+    ks = []
+    for qb in range(50, 66):
+        for _ in range(2):
+            while True:
+                q = rng.randrange(1 << qb, 3 << (qb - 1)) | 1
+                p = rng.randrange(1, q // 8 - 1) | 1
+                if gcd(p, q) == 1:
+                    break
+            for e in (0, 215 - 2 * qb, 225 - 2 * qb, 235 - 2 * qb):
+                if e < 0:
+                    continue
+                for sign in (1, -1):
+                    for j in (0, 1):
+                        ks.append(L8 * p // q + sign * ((1 << e) + j))
+    assert len(ks) == 512 and all(0 < k < L for k in ks)
+    return tuple(ks)
+
+
+@functools.lru_cache(maxsize=None)
+def unbalanced_scalars(n_random=20000):
+    """(a) the structured scalars of the half-size check, (b) scalars at the stop and the Lehmer
+    stop, (c) huge quotients placed there, (d) Fibonacci ratios (runs of quotient 1 ending
+    there), (e) random ones"""
+    ks = list(halfsize_scalars(0))
+    for b in range(186, 207):
+        ks += [(1 << b) - 1, 1 << b, (1 << b) + 1]
+    ks += [STOP_U + d for d in range(-2, 3)] + [ISQRT(1 << 399) + d for d in range(-2, 3)]
+    ks += [(1 << 200) - 1, (1 << 200) + 1]
+    ks += unbalanced_quotient_scalars()
+    for top in (62, 66):
+        fa, fb = 1, 1
+        while fb < 1 << top:
+            fa, fb = fb, fa + fb
+        ks += [(L8 * fa // fb + d) % L for d in range(-32, 33)]
+    rng = random.Random(4321)
+    return tuple(ks + [rng.randrange(L) for _ in range(n_random)])
+
+
+def _bitlens(x):
+    """the bit length of |x|; of a value whose leading 48 bits are all ones also the next one
+    (the header takes bit lengths from fp64 images, which may round up to the power of two:
+    "never underestimates")"""
+    x = abs(x)
+    n = x.bit_length()
+    return {n, n + 1} if (x + (x >> 48)).bit_length() > n else {n}
+
+
+def _cost3(r, t):
+    """what a vector may cost the three-table ladder (sc25519.hpp: bitlen |u| - 128 against bitlen v)"""
+    return {max(a - 128, b) for a in _bitlens(r) for b in _bitlens(t)}
+
+
+@functools.lru_cache(maxsize=None)
+def unbalanced_model(k):
+    """The vectors (u signed, v) sc_unbalanced may return for k, from Python integers: Euclid on
+    (8L, k) with signed cofactors (r_i == t_i k mod 8L) up to the first remainder below 2^191.5;
+    (r1, t1) if t1 is odd, else whichever of b0 = (r0, t0) and b2 = b0 - q b1, q = min(floor(r0 /
+    r1), 2^32 - 1), costs the three-table ladder fewer windows (b0 on a tie).  More than one
+    vector only where the header's fp64 images cannot tell: a remainder within 2^-45 of the
+    stop (either side is taken as it falls), a ratio r0 / r1 within 2^-38 of an integer (lat_quot
+    rounds down by a 2^-40 margin: q or q - 1).  A vector over 250 bits falls back to (k, 1), and so
+    does a sequence of 600 steps (quotients of 2^41 and more before the stop)."""
+    out = set()
+    r0, r1, t0, t1 = L8, k, 0, 1
+    steps = 0  # of the one-step loop: a quotient above 2^32 - 1 is taken in clamped parts
+    while True:
+        # kLatMaxSteps = 600 gives up on the sequence: (k, 1).  The header's count is this one plus one per
+        # quotient that lat_quot's margin splits (ordinary scalars: ~110 steps, none split)
+        if steps >= 584:
+            out.add((k, 1))
+            if steps >= 600:
+                return out
+        near = abs(r1 - STOP_U) <= (STOP_U >> 45)
+        if r1 < STOP_U or near:
+            if t1 & 1:
+                cand = [(r1 if t1 > 0 else -r1, abs(t1))]
+            else:
+                cand = []
+                qs = [0]
+                if r1:
+                    q = r0 // r1
+                    qs = [min(q, 2 ** 32 - 1)]
+                    if q < 2 ** 32 and q > 1 and ((r0 - q * r1) << 38) <= r0:
+                        qs.append(q - 1)
+                for q in qs:
+                    b0, b2 = (r0, t0), (r0 - q * r1, t0 - q * t1)
+                    c0, c2 = _cost3(*b0), _cost3(*b2)
+                    pick = ([b2] if r1 and min(c2) < max(c0) else []) + ([b0] if not r1 or max(c2) >= min(c0) else [])
+                    cand += [(r if t > 0 else -r, abs(t)) for r, t in pick]
+            for u, v in cand:
+                out.add((k, 1) if max(abs(u).bit_length(), v.bit_length()) > 250 else (u, v))
+            if not near:
+                return out
+        q = r0 // r1
+        steps += max(1, -(-q // (2 ** 32 - 1)))
+        r0, r1, t0, t1 = r1, r0 - q * r1, t1, t0 - q * t1
+
+
+def windows3(ubits, vbits):
+    """the window count of a lane of the three-table ladder (ed25519_ops.hpp ladder_uv3)"""
+    return min(64, max(16, (vbits + 5) >> 2, ((ubits + 5) >> 2) - 32))
+
+
+UNBALANCED_WINDOWS_MAX = 32  # what the default host build keeps on every scalar of unbalanced_scalars()
+
+
+def check_unbalanced_properties(ks, res, who):
+    """u == v k (mod 8L) with u signed as reported, v odd, 0 < v < L, bitlen <= bits <= 253 for
+    each of |u| and v, and never more windows than the trivial vector's"""
+    for k, (u, v, ub, vb) in zip(ks, res):
+        assert (u - v * k) % L8 == 0, (who, hex(k))
+        assert v % 2 == 1 and 0 < v < L, (who, hex(k))
+        assert abs(u).bit_length() <= ub <= 253 and v.bit_length() <= vb <= 253, (who, hex(k), ub, vb)
+        w = max(16, (vb + 5) >> 2, ((ub + 5) >> 2) - 32)
+        assert w <= UNBALANCED_WINDOWS_MAX, (who, hex(k), ub, vb, w)
+
+
+def check_unbalanced(run, euclid):
+    """sc_unbalanced_t<true> of the runner (on the GPU: quotients from v_rcp_f64) has the lattice
+    properties, equals the runner's own one-step loop and `euclid` -- the default HOST build's
+    one-step loop on the same scalars -- and is the vector the integer model allows: the
+    remainder pair at 2^191.5 and, for an even cofactor, the cheaper neighbour."""
+    # the construction has not decayed: a quotient >= 2^12 whose dividend (about 8L / q) lies in
+    # 2^190 .. 2^208 -- for qb = 65 (32 of the 512) in 2^189.4 .. 2^190, below the stop already:
+    # there it is the fix-up's quotient
+    in_range = 0
+    for k in unbalanced_quotient_scalars():
+        big = [r0 for r0, _, q in _euclid(k) if q >= 1 << 12 and 1 << 189 <= r0 < 1 << 208]
+        assert big, hex(k)
+        in_range += any(r0 >= 1 << 190 for r0 in big)
+    assert in_range >= 480, in_range
+    ks = unbalanced_scalars()
+    leh = run.sc_unbalanced(ks, 1)
+    check_unbalanced_properties(ks, leh, run.name + " lehmer")
+    one = run.sc_unbalanced(ks, 0)
+    check_unbalanced_properties(ks, one, run.name + " one-step")
+    for k, a, b, c in zip(ks, leh, one, euclid):
+        assert a == b, (run.name, "lehmer != one-step", hex(k), a, b)
+        assert a == c, (run.name, "lehmer != host euclid", hex(k), a, c)
+        assert a[:2] in unbalanced_model(k), (run.name, "not the model's vector", hex(k), a)
+
+
+# --------------------------------------------------------------------------
+# the key-table cache: index, pool and the cached window tables
+# --------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def ktab_keys():
+    """(encodings in lane order, kind per encoding).  One random key on lanes 0 .. 4 of wave 0 (one
+    CAS winner, one entry), 23 more random points, the 8 torsion points (y = 1 and y = -1, x = 0,
+    among them), 7 mixed-order points T + aB, the non-canonical encodings of the model (y + p,
+    negative zero) and 8 undecodable encodings: two waves."""
+    M = model()
+    rng = random.Random(55)
+    rnd = [M.encode(M.pmul(rng.randrange(1, M.L), M.BASE)) for _ in range(24)]
+    keys = [(rnd[0], "random")] * 5 + [(e, "random") for e in rnd[1:]]
+    keys += [(M.encode(t), "torsion") for t in M.TORSION]
+    keys += [(M.encode(M.padd(t, M.pmul(rng.randrange(1, M.L), M.BASE))), "mixed") for t in M.TORSION[1:]]
+    keys += [(e, "noncanonical") for e in M.noncanonical_encodings()]
+    y = 2
+    while sum(kind == "undecodable" for _, kind in keys) < 8:
+        e = (y | (y & 1) << 255).to_bytes(32, "little")
+        if M.decode(e) is None:
+            keys.append((e, "undecodable"))
+        y += 1
+    assert 64 < len(keys) <= 128 and len(set(e for e, _ in keys)) == len(keys) - 4
+    assert M.encode(M.IDENT) in [e for e, _ in keys] and (P - 1).to_bytes(32, "little") in [e for e, _ in keys]
+    return tuple(e for e, _ in keys), tuple(kind for _, kind in keys)
+
+
+@functools.lru_cache(maxsize=None)
+def ktab_expected():
+    """per distinct key: None (undecodable) or (is_small, {(t, d): encode(d [2^(64 t)]A)}), d = -8 .. 8"""
+    M = model()
+    want = {}
+    for e in dict.fromkeys(ktab_keys()[0]):
+        A = M.decode(e)
+        if A is None:
+            want[e] = None
+            continue
+        tab = {}
+        for t in range(3):
+            base = M.pmul(1 << (64 * t), A)
+            acc = M.IDENT
+            tab[(t, 0)] = M.encode(M.IDENT)
+            for d in range(1, 9):
+                acc = M.padd(acc, base)
+                tab[(t, d)], tab[(t, -d)] = M.encode(acc), M.encode(M.pneg(acc))
+        want[e] = (M.is_small(A), tab)
+    return want
+
+
+KT_CAPACITY = 128
+
+
+def _slot_state(blob, slot):
+    return int(blob[KT_CTL_BYTES:KT_POOL_OFF].view(np.uint64)[slot]) >> 32
+
+
+def ktab_filled(run):
+    """the runner's table of ktab_keys(), filled once by one ktab_fill call: (blob, slots won,
+    entry index per key).  Kept on the runner: check_ktab_tables and check_ladder3 read the same table."""
+    if not hasattr(run, "_ktab"):
+        keys, _ = ktab_keys()
+        blob = ktab_blob(KT_CAPACITY)
+        slots = run.ktab_fill(keys, blob, KT_CAPACITY)
+        seen = run.ktab_point(keys, [(0, 1)] * len(keys), blob, KT_CAPACITY)  # a second call: a second launch
+        run._ktab = (blob, slots, {k: s[0] for k, s in zip(keys, seen)})
+    return run._ktab
+
+
+def check_ktab_tables(run):
+    """ktab_probe / ktab_take / ktab_build over the runner's key table, then what a reader finds:
+    one entry per distinct key, every key ready with its tag and the model's flags, and every
+    cached point -- through tab_load_signed and straight from the pool's bytes -- the model's
+    d [2^(64 t)]A.  Then a pool of 4 entries: 4 entries, nothing past them, losers left as seen."""
+    keys, kinds = ktab_keys()
+    want = ktab_expected()
+    distinct = list(want)
+    blob, slots, idx_of = ktab_filled(run)
+    assert int(blob[:4].view(np.uint32)[0]) == len(distinct), (run.name, "pool used")
+    for k in distinct:  # one CAS winner per key, and its slot names the entry
+        won = [s for kk, s in zip(keys, slots) if kk == k and s != KT_NO_SLOT]
+        assert len(won) == 1 and won[0] < KT_SLOTS, (run.name, k.hex(), won)
+        assert _slot_state(blob, won[0]) == KT_READY0 + idx_of[k], (run.name, k.hex())
+    assert sorted(idx_of[k] for k in distinct) == list(range(len(distinct))), (run.name, "entry indices")
+    items = [(k, (t, d)) for k in distinct for t in range(3) for d in range(-8, 9)]
+    got = run.ktab_point([k for k, _ in items], [td for _, td in items], blob, KT_CAPACITY)
+    n_small = n_dead = 0
+    for (k, td), (idx, same, flags, enc) in zip(items, got):
+        assert idx == idx_of[k] and same == 1, (run.name, k.hex(), td, idx, same)
+        if want[k] is None:
+            assert flags == KT_UNDECODABLE, (run.name, k.hex(), flags)
+            n_dead += 1
+            continue
+        small, tab = want[k]
+        assert flags == (KT_SMALL_ORDER if small else 0), (run.name, k.hex(), flags)
+        n_small += small
+        assert enc == tab[td], (run.name, k.hex(), "table", td[0], "digit", td[1])
+    assert n_small >= 8 * 51 and n_dead == 8 * 51
+    # the pool's bytes: point j of table t sits at entry + 128 + (8 t + j - 1) 160 as (Y+X, Y-X, 2Z, 2dT)
+    pool = blob[KT_POOL_OFF:].view(np.uint32)
+    for k in distinct:
+        e0 = idx_of[k] * KT_ENTRY_BYTES // 4
+        assert pool[e0:e0 + 8].tobytes() == k, (run.name, k.hex(), "tag")
+        if want[k] is None:
+            continue
+        for t in range(3):
+            for j in range(1, 9):
+                w = pool[e0 + KT_HEADER_BYTES // 4 + (8 * t + j - 1) * 40:][:40]
+                ypx, ymx, z2 = value(w[:10]), value(w[10:20]), value(w[20:30])
+                zi = pow(z2, P - 2, P)
+                x, y = (ypx - ymx) * zi % P, (ypx + ymx) * zi % P
+                assert (y | (x & 1) << 255).to_bytes(32, "little") == want[k][1][(t, j)], (run.name, k.hex(), t, j)
+                assert (value(w[30:]) * z2 - model().D * (ypx * ypx - ymx * ymx)) % P == 0, (run.name, k.hex(), t, j)
+    # a pool of 4 entries, the keys again in a fresh table
+    cap = 4
+    blob4 = ktab_blob(cap)
+    slots4 = run.ktab_fill(keys, blob4, cap)
+    seen = run.ktab_point(keys, [(0, 1)] * len(keys), blob4, cap)
+    ready = {k: s[0] for k, s in zip(keys, seen) if s[0] != KT_NO_SLOT}
+    assert sorted(ready.values()) == list(range(cap)), (run.name, sorted(ready.values()))
+    for k, s, (idx, same, _, enc) in zip(keys, slots4, seen):
+        if idx != KT_NO_SLOT:
+            assert idx < cap and same == 1, (run.name, k.hex(), idx)
+            assert want[k] is None or enc == want[k][1][(0, 1)], (run.name, k.hex())
+        elif s != KT_NO_SLOT:  # a loser that had won a slot: seen for good
+            assert _slot_state(blob4, s) == KT_SEEN, (run.name, k.hex(), _slot_state(blob4, s))
+    states = blob4[KT_CTL_BYTES:KT_POOL_OFF].view(np.uint64) >> np.uint64(32)
+    assert sorted(int(s) for s in states[states >= KT_READY0]) == [KT_READY0 + i for i in range(cap)], run.name
+    assert not np.any(states == KT_CLAIMED), (run.name, "a slot left claimed")
+
+
+# --------------------------------------------------------------------------
+# the three-table ladder with lane-mixed window counts
+# --------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def ladder3_cases(unbalanced, halfsize):
+    """(A encodings, R encodings, (u, v, ubits, vbits, dead) per lane, expected encodings) of
+    five waves; unbalanced(ks) -> (u, v, ubits, vbits), halfsize(ks) -> (u, v, bits, ...) per
+    scalar: the HOST reductions."""
+    M = model()
+    keys, kinds = ktab_keys()
+    of = lambda kind: [k for k, x in dict(zip(keys, kinds)).items() if x == kind]
+    # the seed: wave 0 gets three lanes of 18 windows (1.2 % of random scalars) beside 17s, and the
+    # balanced vectors of wave 1 are 127 or 128 bits long (33 windows)
+    rng = random.Random(76)
+    pt = lambda: M.encode(M.pmul(rng.randrange(1, M.L), M.BASE))
+    ks = [rng.randrange(L) for _ in range(320)]
+    ub = unbalanced(tuple(ks))
+    hs = halfsize(tuple(ks))
+    win = [windows3(x[2], x[3]) for x in ub]
+    # wave 0 mixes 17-window lanes with longer ones
+    assert sum(w >= 18 for w in win[:64]) >= 3 and sum(w == 17 for w in win[:64]) >= 32, win[:64]
+    hand_u = [0] + [s * m for m in ((1 << 64) - 1, 1 << 64, (1 << 128) - 1, 1 << 128, (1 << 192) - 1, (1 << 194) - 1, 1)
+                    for s in (1, -1)]
+    hand_u += [int(c * n, 16) for c in "87f" for n in (16, 17, 32, 33, 48)]
+    hand_v = [1, (1 << 64) - 1, (1 << 66) - 1, (1 << 128) - 1]
+    tors = [M.encode(t) for t in M.TORSION]
+    As, Rs, vecs = [], [], []
+    for i in range(320):
+        wave, lane = divmod(i, 64)
+        A, R, x = of("random")[i % 24], pt(), ub[i] + (0,)
+        if wave == 1 and lane in (0, 17, 63):
+            x = (ks[i], 1, 253, 1, 0)                    # the trivial vector: 32 windows
+        if wave == 1 and lane in (5, 40):
+            x = (hs[i][0], hs[i][1], hs[i][2], hs[i][2], 0)  # the balanced vector: 33 windows
+            assert windows3(x[2], x[3]) == 33, x
+        if wave == 2:
+            u, v = hand_u[lane % len(hand_u)], hand_v[(lane // len(hand_u) + lane) % 4]
+            if lane == 63:
+                u, v = L - 1, L - 2                      # the upper clamp: 64 windows
+            x = (u, v, abs(u).bit_length(), v.bit_length(), 0)
+        if wave == 3:
+            A = (tors + of("mixed"))[lane % 15]
+            R = (tors + [M.encode(M.IDENT)])[(lane // 3) % 9]
+        if wave == 4:
+            A, x = of("undecodable")[lane % 8], x[:4] + (1,)
+        As.append(A)
+        Rs.append(R)
+        vecs.append(x)
+    assert windows3(*vecs[64][2:4]) == 32 and windows3(*vecs[191][2:4]) == 64
+    assert {u < 0 for u, *_ in vecs[192:256]} == {True, False}
+    want = []
+    for A, R, (u, v, _, _, dead) in zip(As, Rs, vecs):
+        r = M.pmul(v, M.pneg(M.decode(R)))
+        if not dead:
+            a = M.decode(A)
+            r = M.padd(M.pmul(abs(u), a if u < 0 else M.pneg(a)), r)
+        want.append(M.encode(r))
+    return tuple(As), tuple(Rs), tuple(vecs), tuple(want)
+
+
+def check_ladder3(run, unbalanced, halfsize):
+    """-[u]A - [v]R per lane through the key's three cached tables (ladder_uv3: recoding, window
+    rule, wave_max, ladder_a3r) equals the model's: unbalanced vectors of mixed window counts,
+    the trivial and the balanced vector beside them, hand vectors at the 16- and 32-digit string
+    boundaries and both clamps, torsion and mixed-order keys, and dead keys (-[v]R alone)"""
+    As, Rs, vecs, want = ladder3_cases(unbalanced, halfsize)
+    blob, _, idx_of = ktab_filled(run)
+    got = run.ladder_uv3([idx_of[A] for A in As], Rs, vecs, blob, KT_CAPACITY)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (run.name, "wave", i // 64, "lane", i % 64, vecs[i])

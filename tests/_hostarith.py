@@ -41,6 +41,11 @@ def host_halfsize(ks):
     return runner("").sc_halfsize(ks, 1)
 
 
+def host_unbalanced(ks):
+    """sc_unbalanced (the kernels' Lehmer form) of the default host build: (u, v, ubits, vbits) per scalar"""
+    return runner("").sc_unbalanced(ks, 1)
+
+
 def gcd_neg_count(limbs, variant=""):
     """how often the inversion of this value negates a matrix row (gcd_lincomb_shift's rare branch)"""
     return int(load_variant(variant).nth_gcd_neg_count(arr(limbs)))

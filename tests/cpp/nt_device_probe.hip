@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 
 #include "../../narwhal-tusk_amd/csrc/kernels_common.hpp"
 #include "nt_probe_items.hpp"
@@ -132,9 +133,60 @@ __global__ void __launch_bounds__(kBlock)
   ntp::item_ladder_uv(i < n ? i : n - 1, A, R, u, uneg, v, bits, at, o, i < n);
 }
 
+template <bool LEHMER>
+__global__ void __launch_bounds__(kBlock) k_sc_unbalanced(uint64_t n, const uint32_t* k, uint32_t* u, uint32_t* uneg,
+                                                          uint32_t* v, int32_t* ubits, int32_t* vbits) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_sc_unbalanced(i, k, u, uneg, v, ubits, vbits, LEHMER ? 1 : 0);
+}
+// The key-table cache kernels: the product's DevKTab over the probe's allocation.
+// ktab_build is wave-uniform, as in verify_n: lanes past n run it on the last key
+// with no claim (they neither probe nor store).
+__global__ void __launch_bounds__(kBlock)
+    k_ktab_fill(uint64_t n, const uint32_t* A, uint32_t* base, uint32_t cap, uint32_t* slot) {
+  const uint64_t i = item_index();
+  const DevKTab kt{base, cap};
+  ntp::item_ktab_fill(i < n ? i : n - 1, A, kt, slot, i < n);
+}
+__global__ void __launch_bounds__(kBlock) k_ktab_point(uint64_t n, const uint32_t* A, const int32_t* td, uint32_t* base,
+                                                       uint32_t cap, uint32_t* out3, uint32_t* enc) {
+  const uint64_t i = item_index();
+  const DevKTab kt{base, cap};
+  if (i < n) ntp::item_ktab_point(i, A, td, kt, out3, enc);
+}
+// lanes past n run the last item again and write nothing (wave_max: see k_ladder_uv)
+__global__ void __launch_bounds__(kBlock)
+    k_ladder_uv3(uint64_t n, const uint32_t* kidx, const uint32_t* R, const uint32_t* u, const uint32_t* v,
+                 const uint32_t* sc4, uint32_t* base, uint32_t cap, uint4* ws, uint32_t* o) {
+  const uint64_t i = item_index();
+  WsATab at{ws, blockIdx.x};
+  const DevKTab kt{base, cap};
+  ntp::item_ladder_uv3(i < n ? i : n - 1, kidx, R, u, v, sc4, at, kt, o, i < n);
+}
+
+// The probe's key table on the device: `blob` (ktab_probe_bytes(cap) bytes, owned by the
+// caller) copied in, words 4..6 of the control block -- the pool's address and slots - 1 --
+// written from the host before the launch, and copied back after it with those three zeroed.
+struct DevBlob {
+  Dev d;
+  uint8_t* host;
+  size_t bytes;
+  DevBlob(hipError_t* e, uint8_t* blob, uint32_t cap) : d(e, blob, ntp::ktab_probe_bytes(cap)), host(blob),
+                                                        bytes(ntp::ktab_probe_bytes(cap)) {
+    if (*e != hipSuccess) return;
+    const unsigned long long pool = (unsigned long long)(uintptr_t)((uint8_t*)d.p + ntp::kKtProbePoolOff);
+    const uint32_t w[3] = {(uint32_t)pool, (uint32_t)(pool >> 32), ntp::kKtProbeSlots - 1u};
+    *e = hipMemcpy((uint8_t*)d.p + 16, w, sizeof w, hipMemcpyHostToDevice);
+  }
+  void back() const {
+    d.back(host, bytes);
+    if (*d.err == hipSuccess) std::memset(host + 16, 0, 12);
+  }
+};
+
 }  // namespace
 
-#define NTP_BEGIN                      \
+#define NTP_BEGIN                     \
   hipError_t err = hipSetDevice(0);    \
   if (n == 0) return (int)err;
 #define NTP_LAUNCH(kernel, ...) \
@@ -288,6 +340,64 @@ int ntp_ladder_uv(uint64_t n, const uint32_t* A8, const uint32_t* R8, const uint
   NTP_LAUNCH(k_ladder_uv, dA.as<uint32_t>(), dR.as<uint32_t>(), du.as<uint32_t>(), dn.as<uint32_t>(),
              dv.as<uint32_t>(), db.as<int32_t>(), dws.as<uint4>(), dout.as<uint32_t>())
   dout.back(out8, 32 * n);
+  return (int)err;
+}
+int ntp_sc_unbalanced(uint64_t n, const uint32_t* k8, uint32_t* u8, uint32_t* uneg, uint32_t* v8, int32_t* ubits,
+                      int32_t* vbits, int lehmer) {
+  NTP_BEGIN
+  Dev dk(&err, k8, 32 * n), du(&err, nullptr, 32 * n), dn(&err, nullptr, 4 * n), dv(&err, nullptr, 32 * n),
+      dub(&err, nullptr, 4 * n), dvb(&err, nullptr, 4 * n);
+  if (lehmer) {
+    NTP_LAUNCH(k_sc_unbalanced<true>, dk.as<uint32_t>(), du.as<uint32_t>(), dn.as<uint32_t>(), dv.as<uint32_t>(),
+               dub.as<int32_t>(), dvb.as<int32_t>())
+  } else {
+    NTP_LAUNCH(k_sc_unbalanced<false>, dk.as<uint32_t>(), du.as<uint32_t>(), dn.as<uint32_t>(), dv.as<uint32_t>(),
+               dub.as<int32_t>(), dvb.as<int32_t>())
+  }
+  du.back(u8, 32 * n);
+  dn.back(uneg, 4 * n);
+  dv.back(v8, 32 * n);
+  dub.back(ubits, 4 * n);
+  dvb.back(vbits, 4 * n);
+  return (int)err;
+}
+// blob: the key table, ntp::ktab_probe_bytes(capacity) bytes (see DevBlob); one launch per call
+int ntp_ktab_fill(uint64_t n, const uint32_t* A8, uint8_t* blob, uint32_t capacity, uint32_t* slot) {
+  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dA(&err, A8, 32 * n), ds(&err, nullptr, 4 * n);
+  DevBlob db(&err, blob, capacity);
+  NTP_LAUNCH(k_ktab_fill, dA.as<uint32_t>(), db.d.as<uint32_t>(), capacity, ds.as<uint32_t>())
+  ds.back(slot, 4 * n);
+  db.back();
+  return (int)err;
+}
+int ntp_ktab_point(uint64_t n, const uint32_t* A8, const int32_t* td2, uint8_t* blob, uint32_t capacity,
+                   uint32_t* out3, uint32_t* enc8) {
+  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap || !ntp::ktab_point_args_ok(n, td2)) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dA(&err, A8, 32 * n), dt(&err, td2, 8 * n), do3(&err, nullptr, 12 * n), de(&err, nullptr, 32 * n);
+  DevBlob db(&err, blob, capacity);
+  NTP_LAUNCH(k_ktab_point, dA.as<uint32_t>(), dt.as<int32_t>(), db.d.as<uint32_t>(), capacity, do3.as<uint32_t>(),
+             de.as<uint32_t>())
+  do3.back(out3, 12 * n);
+  de.back(enc8, 32 * n);
+  db.back();
+  return (int)err;
+}
+int ntp_ladder_uv3(uint64_t n, const uint32_t* kidx, const uint32_t* R8, const uint32_t* u8, const uint32_t* v8,
+                   const uint32_t* sc4, uint8_t* blob, uint32_t capacity, uint32_t* out8) {
+  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap || !ntp::ladder_uv3_args_ok(n, kidx, sc4, capacity))
+    return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  const size_t ws_bytes = (size_t)grid(n) * kBlock * kAEntries * kAQuads * sizeof(uint4);
+  Dev dk(&err, kidx, 4 * n), dR(&err, R8, 32 * n), du(&err, u8, 32 * n), dv(&err, v8, 32 * n), ds(&err, sc4, 16 * n),
+      dws(&err, nullptr, ws_bytes), dout(&err, nullptr, 32 * n);
+  DevBlob db(&err, blob, capacity);
+  NTP_LAUNCH(k_ladder_uv3, dk.as<uint32_t>(), dR.as<uint32_t>(), du.as<uint32_t>(), dv.as<uint32_t>(),
+             ds.as<uint32_t>(), db.d.as<uint32_t>(), capacity, dws.as<uint4>(), dout.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  db.back();
   return (int)err;
 }
 

@@ -36,6 +36,7 @@ inline double nth_rcp_model(double b) {
 #include "../../narwhal-tusk_amd/csrc/key_table.hpp"
 #include "../../narwhal-tusk_amd/csrc/small_model.hpp"
 #include "nt_probe_items.hpp"
+#include "ktab/host_ktab.hpp"
 
 namespace nt {
 unsigned long long g_fe_mul = 0, g_fe_sq = 0;
@@ -721,6 +722,42 @@ int nthb_ladder_uv(uint64_t n, const uint32_t* A8, const uint32_t* R8, const uin
     if (bits[i] < 0 || bits[i] > 253) return 1;
     HostATab at;
     ntp::item_ladder_uv(i, A8, R8, u8, uneg, v8, bits, at, out8, true);
+  }
+  return 0;
+}
+// lehmer 1: sc_unbalanced_t<true> (verify_one_kt's), 0: the one-step loop
+int nthb_sc_unbalanced(uint64_t n, const uint32_t* k8, uint32_t* u8, uint32_t* uneg, uint32_t* v8, int32_t* ubits,
+                       int32_t* vbits, int lehmer) {
+  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_unbalanced(i, k8, u8, uneg, v8, ubits, vbits, lehmer);
+  return 0;
+}
+// The key-table items over HostKTab (ktab/host_ktab.hpp) on the caller's blob, which has the
+// device's layout: control block, ntp::kKtProbeSlots index slots, `capacity` pool entries.
+static HostKTab blob_ktab(uint8_t* blob, uint32_t capacity) {
+  return HostKTab{(uint64_t*)(blob + ntp::kKtProbeCtlBytes), ntp::kKtProbeSlots - 1u, blob + ntp::kKtProbePoolOff,
+                  capacity, (uint32_t*)blob};
+}
+int nthb_ktab_fill(uint64_t n, const uint32_t* A8, uint8_t* blob, uint32_t capacity, uint32_t* slot) {
+  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap) return 1;
+  const HostKTab kt = blob_ktab(blob, capacity);
+  for (uint64_t i = 0; i < n; ++i) ntp::item_ktab_fill(i, A8, kt, slot, true);
+  return 0;
+}
+int nthb_ktab_point(uint64_t n, const uint32_t* A8, const int32_t* td2, uint8_t* blob, uint32_t capacity,
+                    uint32_t* out3, uint32_t* enc8) {
+  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap || !ntp::ktab_point_args_ok(n, td2)) return 1;
+  const HostKTab kt = blob_ktab(blob, capacity);
+  for (uint64_t i = 0; i < n; ++i) ntp::item_ktab_point(i, A8, td2, kt, out3, enc8);
+  return 0;
+}
+// per item with the item's own window count (wave_max is the identity on the host)
+int nthb_ladder_uv3(uint64_t n, const uint32_t* kidx, const uint32_t* R8, const uint32_t* u8, const uint32_t* v8,
+                    const uint32_t* sc4, uint8_t* blob, uint32_t capacity, uint32_t* out8) {
+  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap || !ntp::ladder_uv3_args_ok(n, kidx, sc4, capacity)) return 1;
+  const HostKTab kt = blob_ktab(blob, capacity);
+  for (uint64_t i = 0; i < n; ++i) {
+    HostATab at;
+    ntp::item_ladder_uv3(i, kidx, R8, u8, v8, sc4, at, kt, out8, true);
   }
   return 0;
 }

@@ -184,4 +184,115 @@ NT_HD NT_INLINE void item_ladder_uv(size_t i, const uint32_t* A8, const uint32_t
   if (write) st_w<8>(out8, i, o);
 }
 
+// sc_unbalanced_t<lehmer>: u, v (8 words), sign of u, bit lengths of |u| and v
+NT_HD NT_INLINE void item_sc_unbalanced(size_t i, const uint32_t* k8, uint32_t* u8, uint32_t* uneg, uint32_t* v8,
+                                        int32_t* ubits, int32_t* vbits, int lehmer) {
+  uint32_t k[8], u[8], v[8], un;
+  int ub, vb;
+  ld_w<8>(k, k8, i);
+  if (lehmer) sc_unbalanced_t<true>(u, un, v, k, ub, vb);
+  else sc_unbalanced_t<false>(u, un, v, k, ub, vb);
+  uneg[i] = un;
+  ubits[i] = ub;
+  vbits[i] = vb;
+  st_w<8>(u8, i, u);
+  st_w<8>(v8, i, v);
+}
+
+// The key-table cache items run over one flat allocation laid out as DevKTab
+// (kernels_common.hpp) reads it: a 128-byte control block, kKtProbeSlots index
+// slots of 8 bytes, then `capacity` pool entries of kKtEntryBytes.
+constexpr uint32_t kKtProbeSlots = 4096, kKtProbeCtlBytes = 128;
+constexpr size_t kKtProbePoolOff = kKtProbeCtlBytes + 8 * (size_t)kKtProbeSlots;
+constexpr uint32_t kKtProbeMaxCap = 1u << 12;
+inline size_t ktab_probe_bytes(uint32_t capacity) { return kKtProbePoolOff + (size_t)capacity * kKtEntryBytes; }
+// the entry points' argument checks, on the host before anything runs: table and digit of
+// every ktab_point item, entry index (below the capacity), flags and bit lengths of every
+// ladder_uv3 item
+inline bool ktab_point_args_ok(uint64_t n, const int32_t* td2) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (td2[2 * i] < 0 || td2[2 * i] >= (int32_t)kKtTables || td2[2 * i + 1] < -8 || td2[2 * i + 1] > 8) return false;
+  return true;
+}
+inline bool ladder_uv3_args_ok(uint64_t n, const uint32_t* kidx, const uint32_t* sc4, uint32_t capacity) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (kidx[i] >= capacity || sc4[4 * i] > 1u || sc4[4 * i + 1] > 253u || sc4[4 * i + 2] > 253u || sc4[4 * i + 3] > 1u)
+      return false;
+  return true;
+}
+
+// The table of item i's key as verify_n makes it: ktab_probe -> ktab_take -> ktab_build.
+// live = false (a lane past n): no probe, no claim, ktab_build's arithmetic alone.
+// slot[i] = the index slot won, or kKtNoSlot.
+template <class KT>
+NT_HD NT_INLINE void item_ktab_fill(size_t i, const uint32_t* A8, const KT& kt, uint32_t* slot, bool live) {
+  uint32_t Aw[8];
+  ld_w<8>(Aw, A8, i);
+  uint32_t claim = kKtNoSlot;
+  if (live) {
+    KtProbe p;
+    ktab_probe(p, Aw, kt);
+    claim = ktab_take(p, kt);
+  }
+  ktab_build(Aw, claim, kt);
+  if (live) slot[i] = claim;
+}
+// What a reader finds for item i's key: out3 = entry index (kKtNoSlot: not ready), tag
+// match, header flags; enc8 = the encoding of the cached point tab_load_signed(idx, t, d)
+// hands out for (t, d) = td2[2 i], td2[2 i + 1], added to the identity.
+template <class KT>
+NT_HD NT_INLINE void item_ktab_point(size_t i, const uint32_t* A8, const int32_t* td2, const KT& kt, uint32_t* out3,
+                                     uint32_t* enc8) {
+  uint32_t Aw[8], o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  ld_w<8>(Aw, A8, i);
+  KtProbe p;
+  ktab_probe(p, Aw, kt);
+  const uint32_t idx = ktab_ready_index(p, kt);
+  uint32_t same = 0, flags = 0;
+  if (idx != kKtNoSlot) {
+    kt.acquire();
+    uint32_t tag[8];
+    kt.hdr_load(idx, tag, flags);
+    same = 1;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) same &= tag[l] == Aw[l];
+    ge_cached ce;
+    kt.tab_load_signed(idx, (uint32_t)td2[2 * i], td2[2 * i + 1], ce);
+    ge_p3 id;
+    ge_p3_0(id);
+    ge_cp c;
+    ge_add_cached(c, id, ce);
+    ge_p2 q;
+    ge_cp_to_p2(q, c);
+    ge_tobytes_w(o, q);
+  }
+  out3[3 * i] = idx;
+  out3[3 * i + 1] = same;
+  out3[3 * i + 2] = flags;
+  st_w<8>(enc8, i, o);
+}
+// verify_uv3's variable-base part: -[u]A - [v]R from the cached tables of pool entry
+// kidx[i] and the lane's own table of -R (ladder_uv3: the recoding, the window rule,
+// wave_max and ladder_a3r); sc4 = uneg, ubits, vbits, dead per item
+template <class ATab, class KT>
+NT_HD NT_INLINE void item_ladder_uv3(size_t i, const uint32_t* kidx, const uint32_t* R8, const uint32_t* u8,
+                                     const uint32_t* v8, const uint32_t* sc4, ATab& at, const KT& kt, uint32_t* out8,
+                                     bool write) {
+  uint32_t Rw[8], u[8], v[8], o[8];
+  ld_w<8>(Rw, R8, i);
+  ld_w<8>(u, u8, i);
+  ld_w<8>(v, v8, i);
+  {
+    ge_p3 R;
+    ge_frombytes_w(R, Rw);
+    ptab_build(R, 1u, at, kTabR);
+  }
+  ge_cp t;
+  ladder_uv3(t, u, sc4[4 * i], v, (int)sc4[4 * i + 1], (int)sc4[4 * i + 2], sc4[4 * i + 3], at, kt, kidx[i]);
+  ge_p2 p;
+  ge_cp_to_p2(p, t);
+  ge_tobytes_w(o, p);
+  if (write) st_w<8>(out8, i, o);
+}
+
 }  // namespace ntp

@@ -5,7 +5,10 @@ signature's accept/reject bit, and every scalar they reach is a SHA-512 output;
 here the device functions get the inputs that stress them directly -- limbs at
 their bounds, chosen wave compositions for the wave-level exits (fe_invert_vt,
 wave_max), scalars with huge partial quotients through the v_rcp_f64 Lehmer
-quotient, messages at every byte alignment.  tests/test_host_arith.py runs the
+quotient, messages at every byte alignment -- and, behind the key-table cache, the
+unbalanced lattice vector with huge quotients at its own stop (2^191.5), the
+product's DevKTab filled and read back point by point, and the three-table ladder
+with chosen digits and window counts.  tests/test_host_arith.py runs the
 same checks on the host build.  Nothing is compiled here: a missing or stale
 probe library fails at once.
 """
@@ -30,7 +33,8 @@ def dev():
 def host():
     """the host build as build() left it (the half-size reference and the ladder's vectors)"""
     lib = os.path.join(H.CPP, "build", "libnthost.so")
-    srcs = [os.path.join(H.CPP, "nt_host_harness.cpp"), os.path.join(H.CPP, "nt_probe_items.hpp")] + \
+    srcs = [os.path.join(H.CPP, "nt_host_harness.cpp"), os.path.join(H.CPP, "nt_probe_items.hpp"),
+            os.path.join(H.CPP, "ktab", "host_ktab.hpp")] + \
         glob.glob(os.path.join(_devprobe.CSRC, "*.hpp"))
     _devprobe.check_fresh(lib, srcs)
     return H.runner("", build=False)
@@ -82,3 +86,15 @@ def test_point_decoding_and_small_order(dev):
 
 def test_ladder_lane_mixed_window_counts(dev, host):
     C.check_ladder(dev, H.host_halfsize)
+
+
+def test_unbalanced_on_device_reciprocal(dev, host):
+    C.check_unbalanced(dev, host.sc_unbalanced(C.unbalanced_scalars(), 0))
+
+
+def test_key_table_entries_and_cached_points(dev):
+    C.check_ktab_tables(dev)
+
+
+def test_three_table_ladder_lane_mixed_window_counts(dev, host):
+    C.check_ladder3(dev, H.host_unbalanced, H.host_halfsize)

@@ -94,6 +94,22 @@ def test_ladder_lane_mixed_window_counts(host):
     C.check_ladder(host, H.host_halfsize)
 
 
+@pytest.mark.parametrize("variant", ["", "_rcp"])
+def test_unbalanced_twin(variant):
+    """the unbalanced lattice vector (the 2^191.5 stop) on the scalars of
+    C.unbalanced_scalars(): both builds, as in test_halfsize_twin, must equal the default
+    build's one-step loop and the integer model"""
+    C.check_unbalanced(H.runner(variant), H.runner("").sc_unbalanced(C.unbalanced_scalars(), 0))
+
+
+def test_key_table_entries_and_cached_points(host):
+    C.check_ktab_tables(host)
+
+
+def test_three_table_ladder_lane_mixed_window_counts(host):
+    C.check_ladder3(host, H.host_unbalanced, H.host_halfsize)
+
+
 def test_device_probe_exports_every_entry():
     """tests/cpp/build/libntprobe.so (the gfx950 build of the same item functions)
     exports one ntp_* entry point per check; loading it needs no GPU"""
@@ -103,7 +119,7 @@ def test_device_probe_exports_every_entry():
     lib = _devprobe.load()
     for sym in _devprobe.EXPORTS:
         getattr(lib, sym)
-    assert len(_devprobe.EXPORTS) == 17
+    assert len(_devprobe.EXPORTS) == 21
 
 
 def test_sha512_host_build():
