@@ -22,6 +22,7 @@
 #define NT_HOST_FAST_FE 1
 #define nt nt_lane
 #include "ed25519_ops.hpp"
+#include "signer_ops.hpp"
 #undef nt
 
 namespace nt {
@@ -216,6 +217,42 @@ bool verify(int mode, const uint8_t pk32[32], const uint8_t sig64[64], const uin
   const uint32_t ok = mode == nt_lane::kStrict ? verify_one<nt_lane::kStrict>(A, R, S, msg, len, at, wb)
                                                : verify_one<nt_lane::kCofactorless>(A, R, S, msg, len, at, wb);
   return ok != 0;
+}
+
+// ---- the signer bound to one key (signer_ops.hpp over the host comb) ----
+void signer_key(const uint8_t seed32[32], uint8_t key192[192]) {
+  static_assert(sizeof(SignerKey) == 192, "the key record the device reads");
+  uint32_t sw[8];
+  std::memcpy(sw, seed32, 32);
+  SignerKey k;
+  const HostComb wb{g_comb->data()};
+  signer_key_setup(k, sw, wb);
+  std::memcpy(key192, &k, sizeof k);
+  std::memset(&k, 0, sizeof k);
+}
+
+void sign_fixed(const uint8_t key192[192], const uint8_t digest32[32], uint8_t sig64[64]) {
+  SignerKey k;
+  std::memcpy(&k, key192, sizeof k);
+  uint32_t m[8], Rw[8], s[8];
+  std::memcpy(m, digest32, 32);
+  const HostComb wb{g_comb->data()};
+  sign_fixed_one(Rw, s, k, m, wb);
+  std::memcpy(sig64, Rw, 32);
+  std::memcpy(sig64 + 32, s, 32);
+}
+
+void vote(const uint8_t key192[192], const uint8_t id32[32], uint64_t round, const uint8_t origin32[32],
+          uint8_t out212[212], uint8_t* digest32) {
+  SignerKey k;
+  std::memcpy(&k, key192, sizeof k);
+  uint32_t idw[8], ow[8], rec[kVoteWireWords], dg[8];
+  std::memcpy(idw, id32, 32);
+  std::memcpy(ow, origin32, 32);
+  const HostComb wb{g_comb->data()};
+  vote_one(rec, dg, k, idw, round, ow, wb);
+  std::memcpy(out212, rec, kVoteWireBytes);
+  if (digest32) std::memcpy(digest32, dg, 32);
 }
 
 }  // namespace cpu

@@ -40,6 +40,14 @@ bool verify(int mode, const uint8_t pk32[32], const uint8_t sig64[64], const uin
 // device's key tables decide it; the key registry admits only such keys)
 bool key_decodes(const uint8_t pk32[32]);
 
+// The signer bound to one key (signer_ops.hpp; require init()): the 192-byte key record of a
+// seed (what the device reads, too), the signature of a 32-byte digest with it, and one vote --
+// the 212 wire bytes of PrimaryMessage::Vote and (digest32 nullable) the digest that was signed.
+void signer_key(const uint8_t seed32[32], uint8_t key192[192]);
+void sign_fixed(const uint8_t key192[192], const uint8_t digest32[32], uint8_t sig64[64]);
+void vote(const uint8_t key192[192], const uint8_t id32[32], uint64_t round, const uint8_t origin32[32],
+          uint8_t out212[212], uint8_t* digest32);
+
 // threads the worker pool runs with the caller (min(64, hardware threads)): the
 // most parallelism a host-lane call gets
 int pool_threads();

@@ -61,6 +61,15 @@ hipError_t launch_group_msgs(const uint64_t* d_first, const uint32_t* d_cnt, uin
 hipError_t launch_sign(const uint8_t* d_seed, const uint8_t* d_msg, uint64_t msg_bytes, const uint64_t* d_off,
                        const uint64_t* d_len, uint64_t n, const uint32_t* d_combB, int bbits, uint8_t* d_pk,
                        uint8_t* d_sig, uint32_t max_blocks, hipStream_t s);
+// ---- the signer bound to one key (k_signer.hip, signer.cpp) ----
+// d_key: the 192-byte key record (signer_ops.hpp SignerKey).  id / origin / digest / vote / sig
+// arrays 16-byte aligned, round 8-byte aligned.  One vote per lane into vote[n][212] and, when
+// d_digest is given, digest[n][32]; max_rows / max_blocks cap the grid (rows of 64 / blocks of 256).
+hipError_t launch_signer_votes(const void* d_key, const uint8_t* d_id, const uint64_t* d_round, const uint8_t* d_origin,
+                               uint64_t n, const uint32_t* d_combB, int bbits, uint8_t* d_vote, uint8_t* d_digest,
+                               uint32_t max_rows, hipStream_t s);
+hipError_t launch_signer_digests(const void* d_key, const uint8_t* d_digest, uint64_t n, const uint32_t* d_combB,
+                                 int bbits, uint8_t* d_sig, uint32_t max_blocks, hipStream_t s);
 // wide combs with `bits`-bit digits (a key-comb width, or kBCombBits for B; kBCombFallback = kKeyCombWide).
 // bbits below: the digit width of the comb of B d_combB was built with (kBCombBits / kBCombFallback).
 hipError_t launch_wcomb_build(int bits, const uint32_t* d_enc, uint32_t nkeys, int negate, uint32_t* d_comb,

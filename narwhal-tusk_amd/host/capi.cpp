@@ -16,6 +16,7 @@ namespace {
 struct CoreHandle {
   primary::Committee committee;
   std::unique_ptr<crypto::KeySet> keyset;
+  std::unique_ptr<primary::VoteSigner> signer;
   primary::Core core;
 };
 }  // namespace
@@ -119,6 +120,36 @@ int ntn_core_ingest_receipts(void* p, const uint8_t* data, const uint64_t* off, 
     for (uint64_t i = 0; i < n; ++i) out_codes[i] = (int32_t)r[i];
     if (host_decided) *host_decided = host;
     return 0;
+  } catch (const std::exception&) {
+    return -2;
+  }
+}
+
+// The node's own key of a Core (seed32; null removes it): name32 (nullable) gets the public key.
+int ntn_core_set_signer(void* p, const uint8_t* seed32, uint8_t* name32) {
+  try {
+    auto* h = (CoreHandle*)p;
+    h->core.signer = nullptr;
+    h->signer.reset();
+    if (!seed32) return 0;
+    h->signer = std::make_unique<primary::VoteSigner>(seed32);
+    h->core.signer = h->signer.get();
+    if (name32) std::memcpy(name32, h->signer->name().bytes.data(), 32);
+    return 0;
+  } catch (const std::exception&) {
+    return -2;
+  }
+}
+
+// Core::votes_for: out_votes212 gets m x 212 wire bytes for the headers receipts[selected[k]].
+// Returns 0, -1 for a selected receipt that is no header's, -2 on a backend failure (no signer).
+int ntn_core_votes_for(void* p, const uint8_t* receipts, const uint32_t* selected, uint64_t m, uint8_t* out_votes212) {
+  try {
+    const auto v = ((CoreHandle*)p)->core.votes_for((const nt_msg_receipt*)receipts, selected, (size_t)m);
+    if (!v.empty()) std::memcpy(out_votes212, v.data(), v.size());
+    return 0;
+  } catch (const std::invalid_argument&) {
+    return -1;
   } catch (const std::exception&) {
     return -2;
   }

@@ -19,7 +19,9 @@
 #include <string_view>
 #include <thread>
 
-#include "../../include/ntcrypto.h"
+#include <stdexcept>
+
+#include "../../include/ntsigner.h"
 #include "narwhal.hpp"
 #include "wire.hpp"
 
@@ -681,6 +683,40 @@ std::vector<DagError> Core::ingest_device_receipts(const uint8_t* data, const ui
                                                    current_header.author.bytes.data(), code.data(), receipts),
                "nt_primary_messages_ingest_receipts");
   return finish_on_host(*this, code, data, off, len, n, threads, host_decided);
+}
+
+VoteSigner::VoteSigner(const uint8_t seed32[32]) {
+  check(nts_signer_create(crypto::Backend::global().ctx(), seed32, &h_), "nts_signer_create");
+}
+
+VoteSigner::~VoteSigner() { nts_signer_free(h_); }
+
+crypto::PublicKey VoteSigner::name() const {
+  crypto::PublicKey pk;
+  check(nts_signer_public(h_, pk.bytes.data()), "nts_signer_public");
+  return pk;
+}
+
+std::vector<uint8_t> Core::votes_for(const nt_msg_receipt* receipts, const uint32_t* selected, size_t m) const {
+  if (!signer) throw crypto::BackendError("Core: votes_for needs the node's signer");
+  std::vector<uint8_t> out(m * (size_t)NTS_VOTE_BYTES);
+  if (m == 0) return out;
+  // committee index -> key, in the order of the key cache (the map's)
+  std::vector<const crypto::PublicKey*> key;
+  for (const auto& kv : committee->authorities) key.push_back(&kv.first);
+  std::vector<uint8_t> id(32 * m), origin(32 * m);
+  std::vector<uint64_t> round(m);
+  for (size_t k = 0; k < m; ++k) {
+    const nt_msg_receipt& r = receipts[selected[k]];
+    if (r.kind != 0 || r.author >= key.size()) throw std::invalid_argument("Core::votes_for: not a header's receipt");
+    std::memcpy(&id[32 * k], r.id, 32);
+    round[k] = r.round;
+    std::memcpy(&origin[32 * k], key[r.author]->bytes.data(), 32);
+  }
+  check(nts_votes_sign(crypto::Backend::global().ctx(), signer->handle(), id.data(), round.data(), origin.data(), m,
+                       out.data(), nullptr),
+        "nts_votes_sign");
+  return out;
 }
 
 std::vector<DagError> Core::ingest_pipelined(const uint8_t* data, const uint64_t* off, const uint64_t* len,

@@ -32,6 +32,7 @@
 
 struct nt_msg_receipt;  // include/ntcrypto.h
 struct nt_worker_receipt;
+struct nts_signer;  // include/ntsigner.h
 
 namespace primary {
 
@@ -135,11 +136,26 @@ IngestStats& last_ingest_stats();
 // signature in ONE verify_strict launch and every certificate's votes in ONE
 // verify_batch launch.  (The reference's only state these checks read is the
 // GC round and the header currently being voted on.)
+// The node's own signer on the process's backend (include/ntsigner.h): what Core hands
+// Vote::new as `name` and `signature_service` (core.rs:184-211).  Not constant time.
+struct VoteSigner {
+  explicit VoteSigner(const uint8_t seed32[32]);
+  ~VoteSigner();
+  VoteSigner(const VoteSigner&) = delete;
+  VoteSigner& operator=(const VoteSigner&) = delete;
+  nts_signer* handle() const { return h_; }
+  crypto::PublicKey name() const;
+
+ private:
+  nts_signer* h_ = nullptr;
+};
+
 struct Core {
   const Committee* committee = nullptr;
   Round gc_round = 0;
   Header current_header;
   const crypto::KeySet* cache = nullptr;  // committee key cache (§8(f).4), optional
+  const VoteSigner* signer = nullptr;     // the node's own key, optional (votes_for)
   // staging reused across ingest calls (one ingest at a time per Core, like the
   // reference's single Core task)
   mutable std::shared_ptr<IngestWorkspace> ws, ws_alt;
@@ -183,6 +199,12 @@ struct Core {
   std::vector<DagError> ingest_device_receipts(const uint8_t* data, const uint64_t* off, const uint64_t* len,
                                                size_t n, nt_msg_receipt* receipts, int threads = 1,
                                                size_t* host_decided = nullptr) const;
+  // votes_for: the node's votes for the headers receipts[selected[k]], k < m (records of
+  // ingest_device_receipts; each must be of kind header, else std::invalid_argument): (id,
+  // round, the author's raw key by committee index) gathered from the receipts, ONE
+  // nts_votes_sign call, and back the m x 212 wire bytes of PrimaryMessage::Vote ready to
+  // send.  Which headers deserve a vote (parents, payload, last_voted) is the caller's decision.
+  std::vector<uint8_t> votes_for(const nt_msg_receipt* receipts, const uint32_t* selected, size_t m) const;
   // the batch in chunks of `chunk` messages, two chunks in flight on two
   // workspaces: one chunk's host decode and checks overlap the other's GPU
   // launches.  Same verdicts as ingest (messages are independent).

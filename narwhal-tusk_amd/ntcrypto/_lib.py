@@ -41,6 +41,12 @@ EXPORTED = [
     "nt_key_cache_sync", "nt_key_cache_info", "nt_dev_clock_probe", "nt_dev_ed25519_verify_keyset_groups",
     "nt_primary_messages_ingest", "nt_primary_messages_ingest_receipts", "nt_worker_messages_ingest",
 ]
+# the signer bound to one key (include/ntsigner.h): a prefix of its own, same library
+SIGNER_EXPORTED = [
+    "nts_signer_create", "nts_signer_free", "nts_signer_public", "nts_sign_digests", "nts_votes_sign",
+    "nts_dev_votes_sign",
+]
+VOTE_BYTES = 212              # NTS_VOTE_BYTES: bincode of PrimaryMessage::Vote
 # nt_msg_receipt (include/ntcrypto.h): one 128-byte record per ingested message
 RECEIPT_DTYPE = np.dtype({
     "names": ["code", "kind", "flags", "author", "origin", "np", "nq", "nv", "round", "off_payload", "off_parents",
@@ -144,6 +150,14 @@ def load_library(path=None):
         lib.nt_dev_clock_probe.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_uint32, _vp, _u64p]
         lib.nt_dev_ed25519_verify_keyset_groups.argtypes = [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp,
                                                             _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]
+    if hasattr(lib, "nts_signer_create"):  # absent from older A/B builds (NTCRYPTO_LIB)
+        lib.nts_signer_create.argtypes = [_vp, _u8p, ctypes.POINTER(_vp)]
+        lib.nts_signer_free.argtypes = [_vp]
+        lib.nts_signer_free.restype = None
+        lib.nts_signer_public.argtypes = [_vp, _u8p]
+        lib.nts_sign_digests.argtypes = [_vp, _vp, _u8p, _u64, _u8p]
+        lib.nts_votes_sign.argtypes = [_vp, _vp, _u8p, _u64p, _u8p, _u64, _u8p, _u8p]
+        lib.nts_dev_votes_sign.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp]
     _lib = lib
     return lib
 
@@ -423,6 +437,10 @@ class Backend:
     def keyset(self, pks):
         return Keyset(self, pks)
 
+    # ---- the node's own key ----
+    def signer(self, seed):
+        return Signer(self, seed)
+
     # ---- device-resident (raw device pointers; stream 0 = HIP's NULL stream) ----
     # Message buffers come with their byte size, as in the C ABI: an item whose
     # slice d_msg[off, off + len) lies outside [0, msg_bytes) is never read.
@@ -531,6 +549,73 @@ class Keyset:
         _check(self.be.lib.nt_dev_ed25519_verify_keyset(self.be.ctx, self.h, dev, stream, mode, d_key_idx, d_sig,
                                                         d_msg, int(msg_bytes), d_off, d_len, n, d_out),
                "nt_dev_ed25519_verify_keyset")
+
+
+class Signer:
+    """A signer bound to one key (nts_signer_*, include/ntsigner.h): the node's own
+    votes and header signatures without a key expansion or [a]B per call.  Not
+    constant time.  Close it before its Backend."""
+
+    def __init__(self, backend, seed):
+        self.be = backend
+        seed = np.frombuffer(bytes(seed), np.uint8)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        h = _vp()
+        _check(backend.lib.nts_signer_create(backend.ctx, _p(seed), ctypes.byref(h)), "nts_signer_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.be.lib.nts_signer_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def public(self):
+        pk = np.zeros(32, np.uint8)
+        _check(self.be.lib.nts_signer_public(self.h, _p(pk)), "nts_signer_public")
+        return pk.tobytes()
+
+    def sign_digests(self, digests):
+        """64-byte signatures of n 32-byte digests (SignatureService::request_signature)."""
+        digests = _u8(digests).reshape(-1, 32)
+        n = len(digests)
+        sig = np.zeros((max(n, 1), 64), np.uint8)
+        _check(self.be.lib.nts_sign_digests(self.be.ctx, self.h, _p(digests) if n else None, n, _p(sig)),
+               "nts_sign_digests")
+        return sig[:n]
+
+    def votes(self, ids, rounds, origins, with_digests=False, out=None):
+        """The wire bytes of PrimaryMessage::Vote for headers (ids[i], rounds[i]) of
+        authors origins[i] (raw 32-byte keys): an (n, 212) uint8 array, and with
+        with_digests the (n, 32) Vote digests that were signed.  out: an (n, 212)
+        C-contiguous uint8 array (pageable or Backend.pinned) to fill instead."""
+        ids = _u8(ids).reshape(-1, 32)
+        origins = _u8(origins).reshape(-1, 32)
+        rounds = np.ascontiguousarray(rounds, np.uint64).reshape(-1)
+        n = len(ids)
+        if len(origins) != n or len(rounds) != n:
+            raise ValueError("ids, rounds and origins: one entry per vote")
+        if out is None:
+            out = np.zeros((max(n, 1), VOTE_BYTES), np.uint8)[:n]
+        elif out.dtype != np.uint8 or out.shape != (n, VOTE_BYTES) or not out.flags.c_contiguous:
+            raise ValueError("out: a C-contiguous (n, 212) uint8 array")
+        dg = np.zeros((max(n, 1), 32), np.uint8) if with_digests else None
+        _check(self.be.lib.nts_votes_sign(self.be.ctx, self.h, _p(ids) if n else None, _p(rounds, _u64p) if n else None,
+                                          _p(origins) if n else None, n, _p(out) if n else None,
+                                          _p(dg) if dg is not None else None), "nts_votes_sign")
+        return (out, dg[:n]) if with_digests else out
+
+    def dev_votes(self, dev, stream, d_ids, d_rounds, d_origins, n, d_votes, d_digests=None):
+        """Enqueue the same over device buffers (raw pointers) on `stream` (nts_dev_votes_sign)."""
+        _check(self.be.lib.nts_dev_votes_sign(self.be.ctx, self.h, int(dev), stream, d_ids, d_rounds, d_origins, int(n),
+                                              d_votes, d_digests), "nts_dev_votes_sign")
 
 
 _default = None

@@ -50,6 +50,10 @@ def load():
         lib.ntn_core_ingest_pipelined.argtypes = [ctypes.c_void_p, _u8p, _u64p, _u64p, ctypes.c_uint64, ctypes.c_int,
                                                   ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32)]
         lib.ntn_core_ingest_pipelined.restype = ctypes.c_int
+        lib.ntn_core_set_signer.argtypes = [ctypes.c_void_p, _u8p, _u8p]
+        lib.ntn_core_set_signer.restype = ctypes.c_int
+        lib.ntn_core_votes_for.argtypes = [ctypes.c_void_p, ctypes.c_void_p, _u32p, ctypes.c_uint64, _u8p]
+        lib.ntn_core_votes_for.restype = ctypes.c_int
         lib.ntn_last_ingest_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
         lib.ntn_last_ingest_stats.restype = None
         lib.ntn_batcher_new.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
@@ -161,6 +165,36 @@ class Core:
         if rc != 0:
             raise NtError("ntn_core_ingest: backend failure")
         return codes[:n], (int(dec.value) if device else dec.value)
+
+    def set_signer(self, seed):
+        """The node's own key (32-byte seed; None removes it): returns the public key."""
+        name = np.zeros(32, np.uint8)
+        sp = np.frombuffer(bytes(seed), np.uint8) if seed is not None else None
+        if sp is not None and len(sp) != 32:
+            raise ValueError("seed: 32 bytes")
+        rc = load().ntn_core_set_signer(self._h, sp.ctypes.data_as(_u8p) if sp is not None else None,
+                                        name.ctypes.data_as(_u8p))
+        if rc != 0:
+            raise NtError("ntn_core_set_signer: backend failure")
+        return name.tobytes() if seed is not None else None
+
+    def votes_for(self, receipts, selected):
+        """Core::votes_for: the node's votes for the headers receipts[selected] (records
+        of ingest(..., device="all", receipts=True)), signed in one call: an
+        (m, 212) uint8 array of PrimaryMessage::Vote wire bytes ready to send."""
+        if receipts.dtype != RECEIPT_DTYPE or receipts.ndim != 1 or not receipts.flags.c_contiguous:
+            raise ValueError("receipts: a C-contiguous RECEIPT_DTYPE array")
+        sel = np.ascontiguousarray(selected, np.uint32).reshape(-1)
+        if len(sel) and int(sel.max()) >= len(receipts):
+            raise ValueError("selected: indices into receipts")
+        out = np.zeros((max(len(sel), 1), 212), np.uint8)
+        rc = load().ntn_core_votes_for(self._h, receipts.ctypes.data_as(ctypes.c_void_p), sel.ctypes.data_as(_u32p),
+                                       len(sel), out.ctypes.data_as(_u8p))
+        if rc == -1:
+            raise ValueError("votes_for: a selected receipt is not a header's")
+        if rc != 0:
+            raise NtError("ntn_core_votes_for: backend failure (no signer set?)")
+        return out[:len(sel)]
 
     def ingest_pipelined(self, data, off, ln, threads=8, chunk=25000):
         """Core::ingest_pipelined: chunks of `chunk` messages, two in flight"""
