@@ -1113,19 +1113,9 @@ NT_HD NT_INLINE bool is_strict(uint32_t meta) {
   return MODE == kStrict || (MODE == kMixed && (meta & kKeyWantStrict));
 }
 
-// One cached verification up to R' = [s]B - [k]A (extended), no decompression
-// of A and no doublings: 16 + 16 wide-comb additions.  Returns the s / key flags.
-template <int MODE, class WCombA, class WCombB>
-NT_HD NT_INLINE uint32_t cached_point(ge_p3& acc, uint32_t meta, const uint32_t Aw[8], const uint32_t Rw[8],
-                                      const uint32_t Sw[8], const uint8_t* msg, uint64_t len, const WCombA& ca,
-                                      const WCombB& cb) {
-  uint32_t okj = sc_is_canonical(Sw) & (meta & kKeyDecodes ? 1u : 0u);
-  if (is_strict<MODE>(meta)) okj &= (meta & kKeySmallOrder) ? 0u : 1u;
-  uint32_t k[8];
-  hram_scalar<true>(k, Rw, Aw, msg, len);
-#ifdef NT_EXPERIMENT_KEY_SKIP
-  wcomb_acc<WCombA, true, NT_EXPERIMENT_KEY_SKIP>(acc, k, ca);  // timing only: wrong verdicts
-#else
+// acc = [k](-A) from the key's comb `ca` (of -A), k < L (k is used up); meta = the key's kKey* bits
+template <class WCombA>
+NT_HD NT_INLINE void key_comb_sum(ge_p3& acc, uint32_t k[8], uint32_t meta, const WCombA& ca) {
   if (CombGeom<WCombA::kBits>::kReduced) {
     // [k](-A) = [k - L](-A) + [L](-A): one position fewer; the second term is
     // the identity unless A has a torsion component
@@ -1145,6 +1135,22 @@ NT_HD NT_INLINE uint32_t cached_point(ge_p3& acc, uint32_t meta, const uint32_t 
   } else {
     wcomb_acc<WCombA, true>(acc, k, ca);
   }
+}
+
+// One cached verification up to R' = [s]B - [k]A (extended), no decompression
+// of A and no doublings: 16 + 16 wide-comb additions.  Returns the s / key flags.
+template <int MODE, class WCombA, class WCombB>
+NT_HD NT_INLINE uint32_t cached_point(ge_p3& acc, uint32_t meta, const uint32_t Aw[8], const uint32_t Rw[8],
+                                      const uint32_t Sw[8], const uint8_t* msg, uint64_t len, const WCombA& ca,
+                                      const WCombB& cb) {
+  uint32_t okj = sc_is_canonical(Sw) & (meta & kKeyDecodes ? 1u : 0u);
+  if (is_strict<MODE>(meta)) okj &= (meta & kKeySmallOrder) ? 0u : 1u;
+  uint32_t k[8];
+  hram_scalar<true>(k, Rw, Aw, msg, len);
+#ifdef NT_EXPERIMENT_KEY_SKIP
+  wcomb_acc<WCombA, true, NT_EXPERIMENT_KEY_SKIP>(acc, k, ca);  // timing only: wrong verdicts
+#else
+  key_comb_sum(acc, k, meta, ca);
 #endif
   wcomb_acc(acc, Sw, cb);
   return okj;

@@ -15,7 +15,7 @@
 //   k_group_msgs          per-signature message offset/length of certificate groups
 //   k_ed25519_sign        keygen + RFC 8032 signing (corpus generation / SignatureService
 //                         batch form; crypto/src/lib.rs:163-191) -- not constant time
-//   k_wcomb_bases/fill    wide-comb construction (B once per device, committee keys)
+//   k_wcomb_bases/fill    wide-comb construction (B once per device, committee keys): wcomb_build.hpp
 //   k_clock_probe         diagnostics: the shader clock under a fixed multiply load (bench.py)
 //
 // SIMT design: every lane runs the same window schedule (fixed signed windows,
@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "kernels_common.hpp"
+#include "wcomb_build.hpp"
 
 namespace nt {
 
@@ -202,60 +203,6 @@ __global__ __launch_bounds__(128) void k_sha512_pipe(const uint8_t* __restrict__
     }
     if (act) sha512_put(out, gi, st, ms.ok, bad);
   }
-}
-
-// --------------------------------------------------------------------------
-// Wide-comb construction
-// --------------------------------------------------------------------------
-// One thread per point: decode (or take B), optionally negate, write the
-// kPos bases 2^(W i) P.  meta[key] gets the kKey* bits.  Keys that do not decode get
-// identity bases (every entry the identity; such keys always reject via meta).
-// Reduced-scalar combs (CombGeom::kReduced) also get the point's [L]P entry
-// after their positions and, in meta, kKeyTorsion when it is not the identity.
-template <int W>
-__global__ void k_wcomb_bases(const uint32_t* __restrict__ enc, uint32_t nkeys, int negate,
-                              uint32_t* __restrict__ bases, uint32_t* __restrict__ meta, uint32_t* __restrict__ comb) {
-  const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
-  if (key >= nkeys) return;
-  uint32_t w[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) w[i] = enc[8 * key + i];
-  ge_p3 P;
-  const uint32_t ok = ge_frombytes_w(P, w);
-  uint32_t m = (ok ? kKeyDecodes : 0u) | (ge_is_small_order(P) ? kKeySmallOrder : 0u);
-  if (!ok) ge_p3_0(P);
-  if (negate) {
-    fe_neg(P.X, P.X);
-    fe_carry(P.X);
-    fe_neg(P.T, P.T);
-    fe_carry(P.T);
-  }
-  if (CombGeom<W>::kReduced) {
-    ge_niels q;
-    m |= wcomb_corr(q, P) ? kKeyTorsion : 0u;
-    uint32_t* o = comb + (size_t)key * CombGeom<W>::kWordsPerPoint + CombGeom<W>::kCorrWord;
-#pragma unroll
-    for (int l = 0; l < 10; ++l) { o[l] = q.ypx.v[l]; o[10 + l] = q.ymx.v[l]; o[20 + l] = q.xy2d.v[l]; }
-    o[30] = 0;
-    o[31] = 0;
-  }
-  if (meta) meta[key] = m;
-  wcomb_bases<W>(bases + (size_t)key * CombGeom<W>::kPos * 40, P);
-}
-
-// One thread per (key, position, chunk of 64 entries).
-template <int W>
-__global__ void k_wcomb_fill(const uint32_t* __restrict__ bases, uint32_t nkeys, uint32_t* __restrict__ comb,
-                             uint32_t* __restrict__ tmp) {
-  using G = CombGeom<W>;
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t per_key = (uint64_t)G::kPos * G::kChunks;
-  if (t >= per_key * nkeys) return;
-  const uint32_t key = (uint32_t)(t / per_key);
-  const uint32_t pos = (uint32_t)((t % per_key) / G::kChunks);
-  const uint32_t c = (uint32_t)(t % G::kChunks);
-  uint32_t* dst = comb + key * G::kWordsPerPoint + ((size_t)pos * G::kEntries + 1 + (size_t)kWChunk * c) * kWStride;
-  wcomb_fill<W>(dst, tmp + t * (kWChunk * 10), bases + ((size_t)key * G::kPos + pos) * 40, c);
 }
 
 // --------------------------------------------------------------------------
@@ -493,28 +440,7 @@ hipError_t launch_sign(const uint8_t* d_seed, const uint8_t* d_msg, uint64_t msg
   return hipGetLastError();
 }
 
-// Builds the W-bit wide combs of nkeys points, `batch` keys per fill launch (tmp
-// must hold wcomb_fill_tmp_bytes_per_key(W) * batch bytes; bases nkeys *
-// wcomb_bases_bytes_per_key(W)).
-template <int W>
-static hipError_t wcomb_build(const uint32_t* d_enc, uint32_t nkeys, int negate, uint32_t* d_comb,
-                              uint32_t* d_meta, uint32_t* d_bases, uint32_t* d_tmp, uint32_t batch, hipStream_t s) {
-  using G = CombGeom<W>;
-  hipLaunchKernelGGL(k_wcomb_bases<W>, dim3((nkeys + 63) / 64), dim3(64), 0, s, d_enc, nkeys, negate, d_bases,
-                     d_meta, d_comb);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  for (uint32_t k0 = 0; k0 < nkeys; k0 += batch) {
-    const uint32_t nk = nkeys - k0 < batch ? nkeys - k0 : batch;
-    const uint64_t threads = (uint64_t)nk * G::kPos * G::kChunks;
-    hipLaunchKernelGGL(k_wcomb_fill<W>, dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, s,
-                       d_bases + (size_t)k0 * G::kPos * 40, nk, d_comb + (size_t)k0 * G::kWordsPerPoint, d_tmp);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
+// the builders and wcomb_build<W>: wcomb_build.hpp
 hipError_t launch_wcomb_build(int bits, const uint32_t* d_enc, uint32_t nkeys, int negate, uint32_t* d_comb,
                               uint32_t* d_meta, uint32_t* d_bases, uint32_t* d_tmp, uint32_t batch,
                               hipStream_t s) {
@@ -805,24 +731,7 @@ hipError_t launch_verify_keyset(int mode, const KsTabs& tabs, KsScratch scratch,
   return hipSuccess;
 }
 
-template <int W>
-static size_t comb_size(int what) {
-  using G = CombGeom<W>;
-  switch (what) {
-    case 0: return G::kWordsPerPoint * 4;
-    case 1: return (size_t)G::kPos * 40 * 4;
-    case 2: return (size_t)G::kPos * G::kChunks * kWChunk * 10 * 4;
-    default: return (size_t)std::max<uint64_t>(1, (128u << 10) / ((uint64_t)G::kPos * G::kChunks));
-  }
-}
-static size_t comb_size(int bits, int what) {
-  return bits == kKeyCombReduced  ? comb_size<kKeyCombReduced>(what)
-         : bits == kKeyCombWide   ? comb_size<kKeyCombWide>(what)
-         : bits == kKeyCombMid    ? comb_size<kKeyCombMid>(what)
-         : bits == kKeyCombNarrow ? comb_size<kKeyCombNarrow>(what)
-         : bits == kBCombBits     ? comb_size<kBCombBits>(what)
-                                  : 0;
-}
+// comb_size: wcomb_build.hpp
 size_t wcomb_bytes_per_key(int bits) { return comb_size(bits, 0); }
 size_t wcomb_bases_bytes_per_key(int bits) { return comb_size(bits, 1); }
 size_t wcomb_fill_tmp_bytes_per_key(int bits) { return comb_size(bits, 2); }

@@ -89,7 +89,8 @@ def _p(a):
 
 ENTRIES = ["fe_mul", "fe_sq", "fe_sq_wide", "fe_carry", "fe_tobytes", "fe_frombytes", "fe_invert", "sc_reduce512",
            "sc_muladd", "sc_mul", "sc_reduce_half", "sc_recode_w4", "sc_is_canonical", "sc_halfsize", "hram",
-           "point_checks", "ladder_uv", "sc_unbalanced", "ktab_fill", "ktab_point", "ladder_uv3"]
+           "point_checks", "ladder_uv", "sc_unbalanced", "ktab_fill", "ktab_point", "ladder_uv3", "wcomb_build",
+           "wcomb_free", "wcomb_entries", "wcomb_guard", "wcomb_digits", "wcomb_acc", "key_comb_sum"]
 
 # the probe's key table (tests/cpp/nt_probe_items.hpp, laid out as kernels_common.hpp DevKTab reads it):
 # a 128-byte control block (word 0: entries handed out), KT_SLOTS index slots of 8 bytes
@@ -270,6 +271,72 @@ class Runner:
         out = np.zeros((len(vecs), 8), np.uint32)
         self._call("ladder_uv3", len(vecs), _p(ki), _p(r), _p(u), _p(v), _p(sc), _p(blob), ctypes.c_uint32(capacity),
                    _p(out))
+        raw = out.tobytes()
+        return [raw[i:i + 32] for i in range(0, len(raw), 32)]
+
+    # the wide combs: one comb set is live per library, between wcomb_build and wcomb_free
+    def _raw(self, entry, *args):
+        fn = getattr(self.lib, self.prefix + entry)
+        fn.restype = ctypes.c_int
+        rc = fn(*args)
+        if rc != 0:
+            raise RuntimeError("%s%s returned %d on %s" % (self.prefix, entry, rc, self.name))
+
+    def wcomb_build(self, bits, encs, negate, batch):
+        """builds the `bits`-bit combs of the encodings (negate: of the negated points), `batch` keys per
+        fill launch; the kKey* word per key"""
+        e = np.frombuffer(b"".join(encs), np.uint32).copy()
+        meta = np.zeros(len(encs), np.uint32)
+        self._raw("wcomb_build", ctypes.c_int(bits), ctypes.c_uint32(len(encs)), _p(e), ctypes.c_int(int(negate)),
+                  ctypes.c_uint32(batch), _p(meta))
+        return [int(m) for m in meta]
+
+    def wcomb_free(self):
+        self._raw("wcomb_free")
+
+    def wcomb_guard(self):
+        out = np.zeros(1, np.uint32)
+        self._raw("wcomb_guard", _p(out))
+        return bool(out[0])
+
+    def wcomb_digits(self, bits, xs):
+        """per scalar: (the kPos + 1 signed digits of wcomb_acc's schedule, the number of loads
+        wcomb_acc itself issued for it, their (position, index) in order)"""
+        a = _words(xs)
+        out = np.zeros((len(a), 64), np.uint32)
+        self._raw("wcomb_digits", ctypes.c_int(bits), ctypes.c_uint64(len(a)), _p(a), _p(out))
+        npos = comb_geom(bits)[0]
+        dig = out[:, :npos + 1].astype(np.int32).tolist()
+        loads = out[:, 18:18 + 2 * (npos + 1)].reshape(len(a), npos + 1, 2).tolist()
+        return [(d, int(r[17]), [tuple(x) for x in ld]) for d, r, ld in zip(dig, out, loads)]
+
+    def wcomb_entries(self, items):
+        """(n, 32) words: the 30 limbs WideComb::load hands out for (key, pos, idx) -- idx =
+        COMB_CORR: load_corr -- then words 30 and 31 of the entry as they lie in memory"""
+        k, p, i = (np.array([it[j] for it in items], np.uint32) for j in range(3))
+        out = np.zeros((len(items), 32), np.uint32)
+        self._raw("wcomb_entries", ctypes.c_uint64(len(items)), _p(k), _p(p), _p(i), _p(out))
+        return out
+
+    def wcomb_acc(self, items):
+        """encoding of start + [+-x]P(key) per item (key, x, flags, start encoding); flags bit 0: from the
+        identity (start unused), bit 1: neg_all"""
+        k = np.array([it[0] for it in items], np.uint32)
+        x = _words([it[1] for it in items])
+        f = np.array([it[2] for it in items], np.uint32)
+        st = np.frombuffer(b"".join(it[3] for it in items), np.uint32).copy()
+        out = np.zeros((len(items), 8), np.uint32)
+        self._raw("wcomb_acc", ctypes.c_uint64(len(items)), _p(k), _p(x), _p(f), _p(st), _p(out))
+        raw = out.tobytes()
+        return [raw[i:i + 32] for i in range(0, len(raw), 32)]
+
+    def key_comb_sum(self, items):
+        """encoding of [k](-A) as cached_point forms it from the key's comb, per item (key, meta, k)"""
+        k = np.array([it[0] for it in items], np.uint32)
+        m = np.array([it[1] for it in items], np.uint32)
+        x = _words([it[2] for it in items])
+        out = np.zeros((len(items), 8), np.uint32)
+        self._raw("key_comb_sum", ctypes.c_uint64(len(items)), _p(k), _p(m), _p(x), _p(out))
         raw = out.tobytes()
         return [raw[i:i + 32] for i in range(0, len(raw), 32)]
 
@@ -1001,3 +1068,387 @@ def check_ladder3(run, unbalanced, halfsize):
     got = run.ladder_uv3([idx_of[A] for A in As], Rs, vecs, blob, KT_CAPACITY)
     for i, (g, w) in enumerate(zip(got, want)):
         assert g == w, (run.name, "wave", i // 64, "lane", i % 64, vecs[i])
+
+
+# --------------------------------------------------------------------------
+# the wide combs: construction, digit schedule, sums (ed25519_ops.hpp wcomb_*, wcomb_build.hpp,
+# kernels_common.hpp WideComb)
+# --------------------------------------------------------------------------
+COMB_WIDTHS = (16, 18, 20, 21, 24)   # kKeyCombNarrow / Mid / Wide / Reduced, kBCombBits
+COMB_REDUCED, COMB_B = 21, 24
+COMB_CORR = 0xffffffff               # "the [L]P entry" where an entry index is expected
+KEY_DECODES, KEY_SMALL_ORDER, KEY_TORSION = 1, 2, 4
+HALF_L = (L - 1) // 2
+
+
+def comb_geom(bits):
+    """(positions, chunks per position, entries per position) of CombGeom<bits>"""
+    red = bits == COMB_REDUCED
+    npos = (252 + bits - 1) // bits if red else (254 + bits - 1) // bits
+    chunks = (1 << (bits - 1)) // 64 + (1 if red else 0)
+    return npos, chunks, 64 * chunks + 1
+
+
+def comb_digits(x, bits):
+    """the integer model of wcomb_acc's digit schedule on a 256-bit x: kPos signed radix-2^bits
+    digits (the reduced comb's top one unsigned, no carry out) and the digit behind the last
+    round's reload"""
+    npos = comb_geom(bits)[0]
+    half, carry, out = 1 << (bits - 1), 0, []
+    for j in range(npos + 1):
+        raw = (x & ((1 << bits) - 1)) + carry
+        carry = 1 if raw > half and not (bits == COMB_REDUCED and j == npos - 1) else 0
+        x >>= bits
+        out.append(raw - (carry << bits))
+    return out
+
+
+def comb_in_table(x, bits):
+    return all(abs(d) < comb_geom(bits)[2] for d in comb_digits(x, bits))
+
+
+@functools.lru_cache(maxsize=None)
+def comb_committee():
+    """(encodings, points -- None: undecodable) of the 5-key committee: an honest key of the corpus,
+    a point of order 8, a mixed-order point T + aB, an undecodable encoding, the identity"""
+    M = model()
+    d = np.load(os.path.join(GOLD, "ed25519_corpus.npz"))
+    import json
+    cats = json.load(open(os.path.join(GOLD, "ed25519_corpus.json")))["categories"]
+    honest = next(d["pk"][i].tobytes() for i in range(len(d["cat"])) if cats[int(d["cat"][i])] == "honest")
+    t8 = M.TORSION[1]
+    assert M.is_ident(M.pmul(8, t8)) and not M.is_ident(M.pmul(4, t8))
+    y = 2
+    while M.decode(y.to_bytes(32, "little")) is not None:
+        y += 1
+    encs = (honest, M.encode(t8), M.encode(M.padd(M.TORSION[3], M.pmul(0x1234567, M.BASE))), y.to_bytes(32, "little"),
+            M.encode(M.IDENT))
+    pts = tuple(M.decode(e) for e in encs)
+    assert [p is None for p in pts] == [False, False, False, True, False]
+    assert [M.has_torsion(p) for p in pts if p is not None] == [False, True, True, False]
+    return encs, pts
+
+
+def _comb_sets(bits):
+    """the comb sets a width is checked on: (encodings, negate, batch, comb point per key)"""
+    M = model()
+    sets = [((M.encode(M.BASE),), 0, 1, (M.BASE,))]
+    if bits != COMB_B:
+        encs, pts = comb_committee()
+        sets.append((encs, 1, 2, tuple(M.IDENT if p is None else M.pneg(p) for p in pts)))
+    return sets
+
+
+def _niels(pt):
+    M = model()
+    X, Y, Z, _ = pt
+    zi = M.inv(Z)
+    x, y = X * zi % P, Y * zi % P
+    return ((y + x) % P, (y - x) % P, 2 * M.D * x * y % P)
+
+
+@functools.lru_cache(maxsize=None)
+def comb_table_cases(bits):
+    """per comb set of the width: (encodings, negate, batch, expected meta -- None: only "does not
+    decode" is pinned --, items (key, pos, idx), expected (y + x, y - x, 2dxy) per item)"""
+    M = model()
+    npos, chunks, entries = comb_geom(bits)
+    regular = (1 << (bits - 1)) // 64
+    chunk_list = [0, 1, regular // 2, regular - 1] + ([chunks - 1] if bits == COMB_REDUCED else [])
+    out = []
+    for encs, negate, batch, pts in _comb_sets(bits):
+        meta = []
+        for e in encs:
+            a = M.decode(e)
+            meta.append(None if a is None else KEY_DECODES | (KEY_SMALL_ORDER if M.is_small(a) else 0) |
+                        (KEY_TORSION if bits == COMB_REDUCED and M.has_torsion(a) else 0))
+        items, want = [], []
+        for key in (0, 2, 4) if len(encs) > 1 else (0,):
+            for pos in (0, 1, npos - 1):
+                base = M.pmul(1 << (bits * pos), pts[key])
+                for c in chunk_list:
+                    q = M.pmul(64 * c, base)
+                    for idx in range(64 * c, 64 * c + 65):
+                        if idx > 64 * c or c == 0:
+                            items.append((key, pos, idx))
+                            want.append(_niels(q))
+                        q = M.padd(q, base)
+        if len(encs) > 1:  # the undecodable key: the identity everywhere
+            for pos in (0, npos - 1):
+                for idx in (0, 1, 64, 65, entries - 1):
+                    items.append((3, pos, idx))
+                    want.append((1, 1, 0))
+        if bits == COMB_REDUCED:  # [L](-A) behind the positions
+            for key in range(len(encs)):
+                items.append((key, 0, COMB_CORR))
+                want.append(_niels(M.pmul(L, pts[key])))
+        out.append((encs, negate, batch, tuple(meta), tuple(items), tuple(want)))
+    return out
+
+
+def check_wcomb_tables(run, bits):
+    """The product's wcomb_build<bits> -- B alone, and (every width but 24) the 5-key committee
+    negated, two keys per fill launch: three launches, the last with one key -- read back
+    through WideComb::load / load_corr: entry (pos, j) is j 2^(bits pos) P for the first, second
+    and last position, the first, second, a middle and the last chunk (21: and the extra one) of
+    keys 0, 2 and 4, words 30 and 31 zero; the identity everywhere for the undecodable key; the
+    kKey* bits; the [L](-A) entry (21); nothing unwritten (the allocation starts as 0xA5) and the
+    guard behind the combs intact.  Returns the number of entries compared."""
+    n = 0
+    for encs, negate, batch, meta, items, want in comb_table_cases(bits):
+        try:
+            got_meta = run.wcomb_build(bits, encs, negate, batch)
+            for k, (g, w) in enumerate(zip(got_meta, meta)):
+                if w is None:
+                    assert not g & KEY_DECODES, (run.name, bits, "key", k, g)
+                else:
+                    assert g == w, (run.name, bits, "meta of key", k, g, w)
+            got = run.wcomb_entries(items)
+            for (key, pos, idx), e, w in zip(items, got, want):
+                g = tuple(value(e[10 * k:10 * k + 10]) % P for k in range(3))
+                assert g == w, (run.name, bits, "key", key, "pos", pos, "entry", idx if idx != COMB_CORR else "corr")
+                assert e[30] == 0 and e[31] == 0, (run.name, bits, key, pos, idx, int(e[30]), int(e[31]))
+            if bits == COMB_REDUCED and len(encs) > 1:
+                assert want[-5] == (1, 1, 0) and want[-4] != (1, 1, 0)  # honest: the identity; order 8: not
+            assert run.wcomb_guard(), (run.name, bits, "guard")
+            n += len(items)
+        finally:
+            run.wcomb_free()
+    return n
+
+
+@functools.lru_cache(maxsize=None)
+def comb_digit_inputs(bits):
+    """(scalars, their model digits)"""
+    npos = comb_geom(bits)[0]
+    half = 1 << (bits - 1)
+    xs = [0, 1, 2 ** 253 - 1, 2 ** 255 - 1, 2 ** 256 - 1, L, L - 1, HALF_L, (L + 1) // 2, 2 ** 251, 2 ** 251 - 1,
+          2 ** 251 + 1]
+    xs.append(sum(half << (bits * i) for i in range(npos - 1)))        # no carry, the maximal index everywhere
+    xs.append(sum((half + 1) << (bits * i) for i in range(npos - 1)))  # a carry through every position
+    if bits == COMB_REDUCED:
+        xs += [t << (bits * (npos - 1)) for t in (2 ** 20, 2 ** 20 + 1, 2 ** 20 + 64)]
+    rng = random.Random(1000 + bits)
+    for i in range(4096):
+        xs.append(rng.randrange(HALF_L + 1) if bits == COMB_REDUCED and i % 2 else rng.getrandbits(256 if i % 4 == 0 else 253))
+    return tuple(xs), tuple(tuple(comb_digits(x, bits)) for x in xs)
+
+
+def check_wcomb_digits(run, bits):
+    """wcomb_digit under wcomb_acc's schedule against the integer model, and the loads wcomb_acc
+    itself issues (a recording comb): position j gets |digit j|, the reload past the last
+    position an in-range index.  The two range facts the headers state: a non-reduced comb never
+    leaves its table for ANY 256-bit input, and sums exactly below 2^253; the reduced comb keeps
+    its top digit <= 2^20 for every magnitude <= (L - 1) / 2 and sums exactly below 2^252.
+    Returns the number of digit vectors compared."""
+    xs, want = comb_digit_inputs(bits)
+    npos, _, entries = comb_geom(bits)
+    half, red = 1 << (bits - 1), bits == COMB_REDUCED
+    # the integer model itself has the properties (so the device is held to them through it)
+    for x, d in zip(xs, want):
+        if not red:
+            assert all(abs(t) <= half for t in d), (bits, hex(x))
+        if x < (1 << 252 if red else 1 << 253):
+            assert sum(t << (bits * i) for i, t in enumerate(d[:npos])) == x and d[npos] == 0, (bits, hex(x))
+        if red and x <= HALF_L:
+            assert all(abs(t) <= half for t in d) and 0 <= d[npos - 1] <= half, hex(x)
+    assert set(want[12][:npos - 1]) == {half} and want[12][npos - 1] == 0                 # the maximal index, no carry
+    assert all(t < 0 for t in want[13][:npos - 1]) and want[13][npos - 1] == 1           # a carry out of every position
+    if red:
+        assert [w[npos - 1] for w in want[14:17]] == [2 ** 20, 2 ** 20 + 1, 2 ** 20 + 64] and max(w[npos - 1] for w in want[14:17]) < entries
+    got = run.wcomb_digits(bits, xs)
+    for x, w, (d, count, loads) in zip(xs, want, got):
+        assert tuple(d) == w, (run.name, bits, hex(x), d, w)
+        assert count == npos + 1, (run.name, bits, hex(x), count)
+        assert loads == [(min(j, npos - 1), abs(t)) for j, t in enumerate(w)], (run.name, bits, hex(x), loads)
+    return len(xs)
+
+
+@functools.lru_cache(maxsize=None)
+def comb_acc_cases(bits):
+    """(encodings, negate, batch, items (key, x, flags, start encoding), expected encodings) on the
+    width's last comb set (the committee; 24: B)"""
+    M = model()
+    encs, negate, batch, pts = _comb_sets(bits)[-1]
+    nk = len(encs)
+    npos, _, entries = comb_geom(bits)
+    red = bits == COMB_REDUCED
+    rng = random.Random(2000 + bits)
+    top = HALF_L + 1 if red else 1 << 253
+    ident = M.encode(M.IDENT)
+    rpt = lambda: M.pmul(rng.randrange(1, L), M.BASE)
+    items, starts = [], []   # starts: the start point (None: from the identity)
+
+    def add(key, x, neg, start):
+        assert comb_in_table(x, bits), (bits, hex(x))
+        items.append((key, x, (1 if start is None else 0) | (2 if neg else 0), ident if start is None else M.encode(start)))
+        starts.append(start)
+
+    def target(key, x, neg):
+        t = M.pmul(x, pts[key])
+        return M.pneg(t) if neg else t
+
+    edges = [x for x in comb_digit_inputs(bits)[0][:14] if x < top] + [0]
+    for x in edges:                                      # edge scalars, both signs, from the identity and added
+        for neg in (0, 1):
+            add(0, x, neg, None)
+            add(2 % nk, x, neg, M.IDENT)
+    for _ in range(3):                                   # first digit zero
+        x = rng.randrange(top) >> bits << bits
+        for neg in (0, 1):
+            add(0, x, neg, None)
+    if red:                                              # the extra chunk: top digit 2^20, +1, +64
+        for t in (2 ** 20, 2 ** 20 + 1, 2 ** 20 + 64):
+            x = (t << (bits * (npos - 1))) + rng.randrange(1 << (bits * (npos - 1) - 1))
+            for neg in (0, 1):
+                add(1, x, neg, None)
+                add(2, x, neg, rpt())
+    for i in range(8):                                   # the four starts
+        x, key = rng.randrange(top), i % nk
+        for neg in (0, 1):
+            add(key, x, neg, M.IDENT)
+            add(key, x, neg, rpt())
+            add(key, x, neg, M.pneg(target(key, x, neg)))    # the sum is the identity
+            add(key, x, neg, target(key, x, neg))            # start = the term itself
+    for pos in (0, 1, npos - 1):                         # one digit: the addition of entry j to j 2^(W pos) P doubles
+        x = rng.randrange(1, max(2, 1 << (min(bits, (252 if red else 253) - bits * pos) - 1))) << (bits * pos)
+        for neg in (0, 1):
+            add(0, x, neg, target(0, x, neg))
+    for i in range(256):                                 # random scalars
+        add(i % nk, rng.randrange(top), rng.getrandbits(1), None if rng.getrandbits(1) else rpt())
+    while len(items) % 64:                               # the wave below starts on a wave boundary
+        add(len(items) % nk, rng.randrange(top), 0, None)
+    for lane in range(64):                               # one wave: its lanes differ in key, sign and start
+        add(lane % nk, rng.randrange(top), (lane // nk) & 1, None if lane % 3 else rpt())
+    want = []
+    for (key, x, flags, _), st in zip(items, starts):
+        t = target(key, x, flags & 2)
+        want.append(M.encode(t if st is None else M.padd(st, t)))
+    return encs, negate, batch, tuple(items), tuple(want)
+
+
+def check_wcomb_acc(run, bits):
+    """out = start + [+-x]P through wcomb_acc over the product's tables (see comb_acc_cases): edge
+    scalars, a zero first digit from the identity, x = 0, the reduced comb's extra chunk, both
+    neg_all values, the four starts, one-digit scalars whose addition is a doubling, random
+    scalars, and a wave whose lanes differ in key and sign.  Returns the number of sums."""
+    encs, negate, batch, items, want = comb_acc_cases(bits)
+    try:
+        run.wcomb_build(bits, encs, negate, batch)
+        got = run.wcomb_acc(items)
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert g == w, (run.name, bits, "wave", i // 64, "lane", i % 64, "key", items[i][0], hex(items[i][1]),
+                            "flags", items[i][2])
+        assert run.wcomb_guard(), (run.name, bits, "guard")
+    finally:
+        run.wcomb_free()
+    return len(items)
+
+
+KEY_SUM_EDGES = (0, 1, 2, HALF_L, (L + 1) // 2, (L + 3) // 2, L - 1, L - 2, (1 << 251) - 1, 1 << 251, (1 << 251) + 1,
+                 (1 << 252) - 1)  # test_reduced_comb_sum_equals_full_comb's
+
+
+@functools.lru_cache(maxsize=None)
+def key_sum_cases():
+    """(items (key, k), expected encodings of [k](-A)) on the committee: whole waves first, chosen by
+    which lanes owe the reduced comb's correction (a key with torsion and k > (L - 1) / 2)"""
+    M = model()
+    encs, pts = comb_committee()
+    rng = random.Random(2121)
+    lo = lambda: rng.randrange(HALF_L + 1)         # k' = k
+    hi = lambda: rng.randrange(HALF_L + 1, L)      # k' = k - L
+    tors, free = (1, 2), (0, 4, 3)                 # keys with / without a torsion component (3: undecodable)
+    items = []
+    for lane in range(64):                         # no lane owes the correction: the branch is skipped
+        items.append((tors[lane % 2], lo()) if lane % 2 else (free[lane % 3], hi()))
+    for owing in (0, 31, 63):                      # exactly one lane owes it
+        for lane in range(64):
+            items.append((tors[lane % 2], hi()) if lane == owing else ((tors[lane % 2], lo()) if lane % 3 else (free[lane % 3], hi())))
+    for lane in range(64):                         # all do
+        items.append((tors[lane % 2], hi()))
+    for lane in range(64):                         # torsion and torsion-free keys alternate, both signs of k - L
+        items.append(((tors + free)[lane % 5] if lane % 2 else free[(lane // 2) % 3], hi() if (lane // 2) % 2 else lo()))
+        if lane % 2 == 0:
+            items[-1] = (tors[(lane // 2) % 2], items[-1][1])
+    for key in range(5):
+        items += [(key, k) for k in KEY_SUM_EDGES]
+    items += [(i % 5, rng.randrange(L)) for i in range(64)]
+    owes = [key in tors and k > HALF_L for key, k in items]
+    assert not any(owes[:64]) and [sum(owes[64 * w:64 * w + 64]) for w in (1, 2, 3)] == [1, 1, 1] and all(owes[256:320])
+    assert owes[64] and owes[128 + 31] and owes[192 + 63] and 8 < sum(owes[320:384]) < 56
+    want = [M.encode(M.IDENT if pts[key] is None else M.pmul(k, M.pneg(pts[key]))) for key, k in items]
+    return tuple(items), tuple(want)
+
+
+def check_key_comb_sum(run):
+    """[k](-A) as cached_point forms it (key_comb_sum: sc_reduce_half, wcomb_acc with neg_all, the
+    wave_any(corr) branch with load_corr) from the 21-bit committee combs and from the 20-bit ones:
+    both equal the model's.  Returns the number of sums per width."""
+    items, want = key_sum_cases()
+    encs, _ = comb_committee()
+    got = {}
+    for bits in (COMB_REDUCED, 20):
+        try:
+            meta = run.wcomb_build(bits, encs, 1, 2)
+            got[bits] = run.key_comb_sum([(key, meta[key], k) for key, k in items])
+        finally:
+            run.wcomb_free()
+        for i, (g, w) in enumerate(zip(got[bits], want)):
+            assert g == w, (run.name, bits, "wave", i // 64, "lane", i % 64, "key", items[i][0], hex(items[i][1]))
+    assert got[COMB_REDUCED] == got[20], run.name
+    return len(items)
+
+
+def check_wcomb_refusals(run):
+    """The comb entry points check their arguments before anything runs: a key past the set, a
+    position or entry past the geometry, the [L]P marker at a width without that entry, an
+    unknown flag, and -- at 21 bits -- a scalar whose digits the integer schedule puts outside
+    the table are refused (an error return, nothing launched); so is any call without a live
+    comb set, and a 24-bit set of more than one point.  Returns the number of refused calls."""
+    M = model()
+    B, ident = M.encode(M.BASE), M.encode(M.IDENT)
+    refused = 0
+
+    def refuses(call, *args):
+        nonlocal refused
+        try:
+            call(*args)
+        except RuntimeError:
+            refused += 1
+            return
+        raise AssertionError((run.name, "not refused", call.__name__, args))
+
+    refuses(run.wcomb_entries, [(0, 0, 0)])                       # no live set
+    refuses(run.wcomb_acc, [(0, 1, 1, ident)])
+    refuses(run.key_comb_sum, [(0, 1, 1)])
+    refuses(run.wcomb_build, COMB_B, (B, B), 0, 1)
+    refuses(run.wcomb_build, COMB_B, (B,), 1, 1)
+    refuses(run.wcomb_build, 17, (B,), 0, 1)
+    refuses(run.wcomb_build, 16, (B,), 0, 0)
+    for bits in (16, COMB_REDUCED):
+        npos, _, entries = comb_geom(bits)
+        try:
+            run.wcomb_build(bits, (B,), 0, 1)
+            good = [(0, npos - 1, entries - 1)]
+            assert len(run.wcomb_entries(good)) == 1
+            for bad in ((1, 0, 0), (0, npos, 0), (0, 0, entries), (0, 0, 2 ** 31)) + (((0, 0, COMB_CORR),) if bits == 16 else ()):
+                refuses(run.wcomb_entries, good + [bad])
+            refuses(run.wcomb_acc, [(0, 1, 1, ident), (1, 1, 1, ident)])
+            refuses(run.wcomb_acc, [(0, 1, 4, ident)])
+            refuses(run.key_comb_sum, [(0, 1, 1), (1, 1, 1)])
+            if bits == COMB_REDUCED:
+                for x in (2 ** 256 - 1, 2 ** 252 - 1, (2 ** 20 + 65) << 231, (2 ** 21 - 1) << 231):
+                    assert not comb_in_table(x, bits), hex(x)
+                    refuses(run.wcomb_acc, [(0, 1, 1, ident), (0, x, 1, ident)])
+                k = 2 ** 253 + 3 * 2 ** 250                     # >= L: sc_reduce_half leaves it as it is
+                assert (L - k) % 2 ** 256 > k and not comb_in_table(k, bits)
+                refuses(run.key_comb_sum, [(0, 1, 1), (0, 1, k)])
+            else:
+                assert comb_in_table(2 ** 256 - 1, bits)
+                assert len(run.wcomb_acc([(0, 2 ** 256 - 1, 1, ident)])) == 1   # any 256-bit input stays inside
+            assert run.wcomb_guard()
+        finally:
+            run.wcomb_free()
+    refuses(run.wcomb_guard)                                       # freed: no live set
+    return refused

@@ -7,6 +7,13 @@
 // with blocks of kBlock = 256 item i sits in wave i / 64, lane i % 64, and a
 // test chooses what shares a wave.  Each ntp_* entry point takes host pointers,
 // works on device 0 and returns the hipError_t (0 = success).
+// Kernels: k_fe_* (multiply, squares, carry, bytes, both inversions), k_sc_* (reduce512,
+// muladd, mul, reduce_half, recode_w4, is_canonical, halfsize, unbalanced), k_hram,
+// k_point_checks, k_ladder_uv, the key-table cache's k_ktab_fill / k_ktab_point /
+// k_ladder_uv3, and the wide combs': k_wcomb_digits (wcomb_digit under wcomb_acc's
+// schedule), k_wcomb_entries (WideComb::load / load_corr), k_wcomb_acc, k_key_comb_sum --
+// the last three over combs that ntp_wcomb_build makes with the product's own
+// k_wcomb_bases / k_wcomb_fill through wcomb_build<W> (csrc/wcomb_build.hpp).
 // Never linked into libntcrypto.so.
 #include <hip/hip_runtime.h>
 
@@ -183,6 +190,63 @@ struct DevBlob {
     if (*d.err == hipSuccess) std::memset(host + 16, 0, 12);
   }
 };
+
+// The wide-comb kernels: the product's WideComb<W> over the probe's comb set (key[i] picks
+// the comb of item i).  Lanes past n leave at once: key_comb_sum's wave_any then sees
+// exactly the lanes the caller filled.
+template <int W>
+__global__ void __launch_bounds__(kBlock) k_wcomb_digits(uint64_t n, const uint32_t* x, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_wcomb_digits<W>(i, x, o);
+}
+template <int W>
+__global__ void __launch_bounds__(kBlock) k_wcomb_entries(uint64_t n, const uint32_t* comb, const uint32_t* key,
+                                                          const uint32_t* pos, const uint32_t* idx, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i >= n) return;
+  const WideComb<W> wc{comb + (size_t)key[i] * CombGeom<W>::kWordsPerPoint};
+  ntp::item_wcomb_entry(i, wc, pos[i], idx[i], o);
+}
+template <int W>
+__global__ void __launch_bounds__(kBlock)
+    k_wcomb_acc(uint64_t n, const uint32_t* comb, const uint32_t* key, const uint32_t* x, const uint32_t* flags,
+                const uint32_t* start, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i >= n) return;
+  const WideComb<W> wc{comb + (size_t)key[i] * CombGeom<W>::kWordsPerPoint};
+  ntp::item_wcomb_acc(i, wc, x, flags, start, o);
+}
+template <int W>
+__global__ void __launch_bounds__(kBlock) k_key_comb_sum(uint64_t n, const uint32_t* comb, const uint32_t* key,
+                                                         const uint32_t* meta, const uint32_t* k, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i >= n) return;
+  const WideComb<W> wc{comb + (size_t)key[i] * CombGeom<W>::kWordsPerPoint};
+  ntp::item_key_comb_sum(i, wc, meta, k, o);
+}
+
+// The probe's comb set: `nkeys` combs of `bits`-bit digits in one allocation, then
+// ntp::kWcGuardBytes of the fill pattern.  One set is live at a time.
+struct WcSet {
+  int bits = 0;
+  uint32_t nkeys = 0;
+  uint8_t* p = nullptr;
+  size_t comb_bytes = 0;
+} g_wc;
+
+void wc_free() {
+  if (g_wc.p) (void)hipFree(g_wc.p);
+  g_wc = WcSet{};
+}
+// the `guard` bytes at d still hold the fill pattern
+bool guard_intact(hipError_t* err, const uint8_t* d, size_t guard) {
+  static uint8_t h[ntp::kWcGuardBytes];
+  if (*err == hipSuccess) *err = hipMemcpy(h, d, guard, hipMemcpyDeviceToHost);
+  if (*err != hipSuccess) return false;
+  for (size_t b = 0; b < guard; ++b)
+    if (h[b] != (uint8_t)ntp::kWcFill) return false;
+  return true;
+}
 
 }  // namespace
 
@@ -398,6 +462,110 @@ int ntp_ladder_uv3(uint64_t n, const uint32_t* kidx, const uint32_t* R8, const u
              ds.as<uint32_t>(), db.d.as<uint32_t>(), capacity, dws.as<uint4>(), dout.as<uint32_t>())
   dout.back(out8, 32 * n);
   db.back();
+  return (int)err;
+}
+
+// ---- the wide combs.  Every index a kernel below forms is checked here, on the host, against
+// the live comb set before anything is launched (ntp::*_args_ok): nothing out of range reaches
+// the GPU.
+// Builds the combs of nkeys encodings (negate: of the negated points) with the product's
+// wcomb_build<W>, `batch` keys per fill launch and the scratch sizes the product allocates for
+// that batch, into an allocation pre-filled with 0xA5 that stays alive until ntp_wcomb_free or
+// the next build; meta_out = the kKey* words.  The builders' scratch (bases, tmp) is followed by
+// the same guard pattern: hipErrorUnknown if a build wrote past either.
+int ntp_wcomb_build(int bits, uint32_t nkeys, const uint32_t* enc8, int negate, uint32_t batch, uint32_t* meta_out) {
+  if (!ntp::wcomb_build_args_ok(bits, nkeys, negate, batch)) return (int)hipErrorInvalidValue;
+  hipError_t err = hipSetDevice(0);
+  wc_free();
+  const size_t comb_bytes = comb_size(bits, 0) * nkeys, bases_bytes = comb_size(bits, 1) * nkeys,
+               tmp_bytes = comb_size(bits, 2) * (batch < nkeys ? batch : nkeys), guard = ntp::kWcGuardBytes;
+  if (err == hipSuccess) err = hipMalloc((void**)&g_wc.p, comb_bytes + guard);
+  if (err != hipSuccess) {
+    g_wc = WcSet{};
+    return (int)err;
+  }
+  g_wc.bits = bits;
+  g_wc.nkeys = nkeys;
+  g_wc.comb_bytes = comb_bytes;
+  err = hipMemset(g_wc.p, ntp::kWcFill, comb_bytes + guard);
+  Dev de(&err, enc8, 32 * (size_t)nkeys), dm(&err, nullptr, 4 * (size_t)nkeys), db(&err, nullptr, bases_bytes + guard),
+      dt(&err, nullptr, tmp_bytes + guard);
+  if (err == hipSuccess) err = hipMemset((uint8_t*)db.p + bases_bytes, ntp::kWcFill, guard);
+  if (err == hipSuccess) err = hipMemset((uint8_t*)dt.p + tmp_bytes, ntp::kWcFill, guard);
+  if (err == hipSuccess)
+    ntp::wcomb_width(bits, [&](auto w) {
+      err = wcomb_build<decltype(w)::value>(de.as<uint32_t>(), nkeys, negate, (uint32_t*)g_wc.p, dm.as<uint32_t>(),
+                                            db.as<uint32_t>(), dt.as<uint32_t>(), batch, 0);
+    });
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  dm.back(meta_out, 4 * (size_t)nkeys);
+  const bool scratch_ok = guard_intact(&err, (uint8_t*)db.p + bases_bytes, guard) &&
+                          guard_intact(&err, (uint8_t*)dt.p + tmp_bytes, guard);
+  if (err == hipSuccess && !scratch_ok) err = hipErrorUnknown;
+  if (err != hipSuccess) wc_free();
+  return (int)err;
+}
+int ntp_wcomb_free() {
+  wc_free();
+  return 0;
+}
+// out1 = 1: the guard after the live comb set still holds the fill pattern
+int ntp_wcomb_guard(uint32_t* out1) {
+  if (!g_wc.p) return (int)hipErrorInvalidValue;
+  hipError_t err = hipSetDevice(0);
+  *out1 = guard_intact(&err, g_wc.p + g_wc.comb_bytes, ntp::kWcGuardBytes) ? 1u : 0u;
+  return (int)err;
+}
+// needs no table (the loads go to a recording comb): any 256-bit x
+int ntp_wcomb_digits(int bits, uint64_t n, const uint32_t* x8, uint32_t* out) {
+  if (!ntp::wcomb_width(bits, [](auto) {})) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dx(&err, x8, 32 * n), dout(&err, nullptr, 4 * ntp::kWcDigitWords * n);
+  ntp::wcomb_width(bits, [&](auto w) {
+    NTP_LAUNCH(k_wcomb_digits<decltype(w)::value>, dx.as<uint32_t>(), dout.as<uint32_t>())
+  });
+  dout.back(out, 4 * ntp::kWcDigitWords * n);
+  return (int)err;
+}
+int ntp_wcomb_entries(uint64_t n, const uint32_t* key, const uint32_t* pos, const uint32_t* idx, uint32_t* out32) {
+  bool ok = false;
+  ntp::wcomb_width(g_wc.bits, [&](auto w) { ok = ntp::wcomb_entry_args_ok<decltype(w)::value>(n, g_wc.nkeys, key, pos, idx); });
+  if (!g_wc.p || !ok) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dk(&err, key, 4 * n), dp(&err, pos, 4 * n), di(&err, idx, 4 * n), dout(&err, nullptr, 128 * n);
+  ntp::wcomb_width(g_wc.bits, [&](auto w) {
+    NTP_LAUNCH(k_wcomb_entries<decltype(w)::value>, (const uint32_t*)g_wc.p, dk.as<uint32_t>(), dp.as<uint32_t>(),
+               di.as<uint32_t>(), dout.as<uint32_t>())
+  });
+  dout.back(out32, 128 * n);
+  return (int)err;
+}
+int ntp_wcomb_acc(uint64_t n, const uint32_t* key, const uint32_t* x8, const uint32_t* flags, const uint32_t* start_enc8,
+                  uint32_t* out_enc8) {
+  bool ok = false;
+  ntp::wcomb_width(g_wc.bits, [&](auto w) { ok = ntp::wcomb_acc_args_ok<decltype(w)::value>(n, g_wc.nkeys, key, x8, flags); });
+  if (!g_wc.p || !ok) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dk(&err, key, 4 * n), dx(&err, x8, 32 * n), df(&err, flags, 4 * n), ds(&err, start_enc8, 32 * n),
+      dout(&err, nullptr, 32 * n);
+  ntp::wcomb_width(g_wc.bits, [&](auto w) {
+    NTP_LAUNCH(k_wcomb_acc<decltype(w)::value>, (const uint32_t*)g_wc.p, dk.as<uint32_t>(), dx.as<uint32_t>(),
+               df.as<uint32_t>(), ds.as<uint32_t>(), dout.as<uint32_t>())
+  });
+  dout.back(out_enc8, 32 * n);
+  return (int)err;
+}
+int ntp_key_comb_sum(uint64_t n, const uint32_t* key, const uint32_t* meta, const uint32_t* k8, uint32_t* out_enc8) {
+  bool ok = false;
+  ntp::wcomb_width(g_wc.bits, [&](auto w) { ok = ntp::key_comb_args_ok<decltype(w)::value>(n, g_wc.nkeys, key, k8); });
+  if (!g_wc.p || !ok) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dk(&err, key, 4 * n), dm(&err, meta, 4 * n), ds(&err, k8, 32 * n), dout(&err, nullptr, 32 * n);
+  ntp::wcomb_width(g_wc.bits, [&](auto w) {
+    NTP_LAUNCH(k_key_comb_sum<decltype(w)::value>, (const uint32_t*)g_wc.p, dk.as<uint32_t>(), dm.as<uint32_t>(),
+               ds.as<uint32_t>(), dout.as<uint32_t>())
+  });
+  dout.back(out_enc8, 32 * n);
   return (int)err;
 }
 

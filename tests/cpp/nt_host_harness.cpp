@@ -3,8 +3,9 @@
 // CPU-only tests can (a) stress the radix-2^25.5 bound discipline with
 // adversarial limb values against Python big integers, (b) replay the golden
 // corpus through the same verify_n<> / verify_cached_n<> the kernels run,
-// (c) check the wide-comb construction (wcomb_bases/wcomb_fill) against an
-// independent curve model, and (d) count field multiplies per operation
+// (c) check the wide-comb construction (wcomb_key_bases / wcomb_fill, driven through
+// wcomb_fill_target and wcomb_fill_launch of wcomb_build.hpp), digit schedule and sums
+// against an independent curve model, and (d) count field multiplies per operation
 // (profiles/opcount.json, the roofline numerator).
 // Never linked into libntcrypto.so.
 #define NT_OPCOUNT 1
@@ -411,20 +412,12 @@ uint32_t nth_key_comb_sum(int bits, const uint8_t* A32, const uint8_t* k32, uint
     static HostKeyCombRed c;
     meta = key_comb(c, Aw);
     c.memo.clear();
-    const uint32_t kneg = sc_reduce_half(k);
-    wcomb_acc<HostCombRef<HostKeyCombRed>, true>(acc, k, HostCombRef<HostKeyCombRed>{&c}, kneg);
-    if (kneg && (meta & kKeyTorsion)) {
-      ge_niels q;
-      c.load_corr(q);
-      ge_cp t;
-      ge_add_niels(t, acc, q);
-      ge_cp_to_p3(acc, t);
-    }
+    key_comb_sum(acc, k, meta, HostCombRef<HostKeyCombRed>{&c});
   } else {
     static HostKeyComb c;
     meta = key_comb(c, Aw);
     c.memo.clear();
-    wcomb_acc<HostCombRef<HostKeyComb>, true>(acc, k, HostCombRef<HostKeyComb>{&c});
+    key_comb_sum(acc, k, meta, HostCombRef<HostKeyComb>{&c});
   }
   finish();
   return meta;
@@ -445,32 +438,21 @@ void nth_sign(const uint8_t* seed, const uint8_t* msg, uint64_t len, uint8_t* pk
 }
 // The device's wide-comb construction run on the host for one chunk: entries
 // j0-1 .. j0+63 (j0 = 1 + 64c; entry j0-1 only written for c = 0) of position
-// pos of the comb of P (negate: of -P), as 65 x 32 words.  Returns kKey* bits.
+// pos of the comb of P (negate: of -P), as 65 x 32 words, for any of the five
+// widths and any chunk of the width (the reduced comb's extra one included).
+// Returns the kKey* bits, ~0 for a width, position or chunk there is not.
 uint32_t nth_wcomb_chunk(int bits, const uint8_t* enc32, int negate, int pos, int c, uint32_t* out) {
-  uint32_t w[8];
+  uint32_t w[8], meta = ~0u;
   words(w, enc32);
-  ge_p3 P;
-  const uint32_t ok = ge_frombytes_w(P, w);
-  const uint32_t meta = (ok ? kKeyDecodes : 0u) | (ge_is_small_order(P) ? kKeySmallOrder : 0u);
-  if (!ok) ge_p3_0(P);
-  if (negate) {
-    fe_neg(P.X, P.X);
-    fe_carry(P.X);
-    fe_neg(P.T, P.T);
-    fe_carry(P.T);
-  }
-  static uint32_t bases[CombGeom<kKeyCombNarrow>::kPos * 40];
-  static uint32_t tmp[kWChunk * 10];
-  std::memset(out, 0, 65 * kWStride * 4);
-  if (bits == kKeyCombWide) {
-    wcomb_bases<kKeyCombWide>(bases, P);
-    wcomb_fill<kKeyCombWide>(out + kWStride, tmp, bases + 40 * pos, (uint32_t)c);
-  } else if (bits == kKeyCombNarrow) {
-    wcomb_bases<kKeyCombNarrow>(bases, P);
-    wcomb_fill<kKeyCombNarrow>(out + kWStride, tmp, bases + 40 * pos, (uint32_t)c);
-  } else {
-    return ~0u;
-  }
+  ntp::wcomb_width(bits, [&](auto wd) {
+    constexpr int W = decltype(wd)::value;
+    using G = CombGeom<W>;
+    if (pos < 0 || pos >= G::kPos || c < 0 || c >= G::kChunks) return;
+    static uint32_t bases[G::kPos * 40], corr[kWStride], tmp[kWChunk * 10];
+    std::memset(out, 0, 65 * kWStride * 4);
+    meta = wcomb_key_bases<W>(w, negate, bases, corr, nullptr);
+    wcomb_fill<W>(out + kWStride, tmp, bases + 40 * pos, (uint32_t)c);
+  });
   return meta;
 }
 // small-order test of a decodable encoding both ways: [8]P by doublings and
@@ -820,5 +802,240 @@ int nth_gcd_neg_count(const uint32_t* f) {
   for (int i = 1; i < 9; ++i) bone |= b[i];
   if (!zero && (anz != 0 || bone != 0)) return -1;
   return count;
+}
+}
+
+// ---- host twins of the probe's wide-comb entry points (nt_device_probe.hip), same argument
+// lists and the same argument checks (ntp::*_args_ok; 1 where the probe returns an error).
+// Digits, sums and key sums run over HostWComb (entries by double-and-add) at all five
+// widths.  Table entries come from the product's construction: at 16 bits from whole combs
+// (67 MB per key) built as wcomb_build<W> builds them -- wcomb_key_bases per key, then per
+// batch (wcomb_fill_launch) every thread of the launch's grid through wcomb_fill_target and
+// wcomb_fill, into an allocation pre-filled with 0xA5 with a guard behind it -- over which the
+// sums run a second time (2: the two disagree); at the other widths from single chunks,
+// filled on demand by the thread wcomb_fill_target names for them.
+namespace {
+template <int W>
+struct HostTabComb {  // a built comb in memory, read as WideComb<W> reads it
+  static constexpr int kBits = W;
+  const uint32_t* base;
+  void get(const uint32_t* e, ge_niels& q) const {
+    for (int l = 0; l < 10; ++l) { q.ypx.v[l] = e[l]; q.ymx.v[l] = e[10 + l]; q.xy2d.v[l] = e[20 + l]; }
+  }
+  void load(uint32_t pos, uint32_t idx, ge_niels& q) const {
+    get(base + ((size_t)pos * CombGeom<W>::kEntries + idx) * kWStride, q);
+  }
+  void load_corr(ge_niels& q) const { get(base + CombGeom<W>::kCorrWord, q); }
+};
+constexpr uint32_t kFillWord = 0x01010101u * (uint32_t)ntp::kWcFill;
+constexpr size_t kGuardWords = ntp::kWcGuardBytes / 4;
+struct HostWcSet {
+  int bits = 0;
+  uint32_t nkeys = 0;
+  std::vector<uint32_t> table, bases, corr, meta;                // table: whole combs (16 bits only)
+  std::unordered_map<uint64_t, std::vector<uint32_t>> chunks;  // fill thread -> entries 64c .. 64c + 64
+  std::vector<uint32_t> args;                                    // what it was built from
+  void clear() { *this = HostWcSet{}; }
+} g_hwc;
+// Whole-comb sets that were freed, kept by their build arguments: a second build of the same
+// set (the checks build the committee once per check; 2 s per key here) takes the tables back
+// instead of filling them again.  Only the tables of a set whose guard was intact are kept.
+std::vector<HostWcSet> g_hwc_kept;
+template <int W>
+std::vector<HostWComb<W>>& host_combs() {
+  static std::vector<HostWComb<W>> v;
+  return v;
+}
+bool words_intact(const uint32_t* p, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (p[i] != kFillWord) return false;
+  return true;
+}
+template <int W>
+int host_wcomb_build(uint32_t nkeys, const uint32_t* enc8, int negate, uint32_t batch, uint32_t* meta_out) {
+  using G = CombGeom<W>;
+  HostWcSet& s = g_hwc;
+  s.clear();
+  std::vector<uint32_t> args = {(uint32_t)W, nkeys, (uint32_t)negate, batch};
+  args.insert(args.end(), enc8, enc8 + 8 * (size_t)nkeys);
+  s.args = args;
+  s.bits = W;
+  s.nkeys = nkeys;
+  s.bases.assign((size_t)nkeys * G::kPos * 40 + kGuardWords, kFillWord);
+  s.corr.assign((size_t)nkeys * kWStride, kFillWord);
+  s.meta.resize(nkeys);
+  auto& hc = host_combs<W>();
+  hc.clear();
+  hc.resize(nkeys);
+  for (uint32_t key = 0; key < nkeys; ++key) {
+    meta_out[key] = s.meta[key] = wcomb_key_bases<W>(enc8 + 8 * key, negate, s.bases.data() + (size_t)key * G::kPos * 40,
+                                                    s.corr.data() + (size_t)key * kWStride, nullptr);
+    ge_p3 P;
+    if (!ge_frombytes_w(P, enc8 + 8 * key)) ge_p3_0(P);
+    if (negate) {
+      fe_neg(P.X, P.X);
+      fe_carry(P.X);
+      fe_neg(P.T, P.T);
+      fe_carry(P.T);
+    }
+    hc[key].init(P);
+  }
+  if (W != kKeyCombNarrow) return words_intact(s.bases.data() + s.bases.size() - kGuardWords, kGuardWords) ? 0 : 3;
+  for (size_t i = 0; i < g_hwc_kept.size(); ++i)
+    if (g_hwc_kept[i].args == args) {
+      s.table = std::move(g_hwc_kept[i].table);
+      g_hwc_kept.erase(g_hwc_kept.begin() + i);
+      return 0;
+    }
+  const size_t tmp_words = comb_size<W>(2) / 4 * (batch < nkeys ? batch : nkeys);
+  std::vector<uint32_t> tmp(tmp_words + kGuardWords, kFillWord);
+  s.table.assign((size_t)nkeys * G::kWordsPerPoint + kGuardWords, kFillWord);
+  for (uint32_t k0 = 0; k0 < nkeys; k0 += batch) {
+    const WCombFillLaunch fl = wcomb_fill_launch<W>(k0, nkeys, batch);
+    const uint64_t grid = (fl.threads + 63) / 64 * 64;
+    for (uint64_t t = 0; t < grid; ++t) {
+      WCombFillTarget ft;
+      if (!wcomb_fill_target<W>(ft, t, fl.nkeys)) continue;
+      if (ft.tmp + kWChunk * 10 > tmp_words || fl.comb_off + ft.dst + (size_t)kWChunk * kWStride > s.table.size() - kGuardWords)
+        return 3;  // the harness refuses what would leave its own allocations
+      wcomb_fill<W>(s.table.data() + fl.comb_off + ft.dst, tmp.data() + ft.tmp,
+                    s.bases.data() + fl.bases_off + ((size_t)ft.key * G::kPos + ft.pos) * 40, ft.chunk);
+    }
+  }
+  return words_intact(tmp.data() + tmp_words, kGuardWords) &&
+                 words_intact(s.bases.data() + s.bases.size() - kGuardWords, kGuardWords)
+             ? 0
+             : 3;
+}
+// entry (pos, idx) of key's comb at a width whose combs are not built whole: the chunk that
+// holds it, filled once by the thread wcomb_fill_target maps to (key, pos, chunk)
+template <int W>
+const uint32_t* host_chunk_entry(uint32_t key, uint32_t pos, uint32_t idx) {
+  using G = CombGeom<W>;
+  HostWcSet& s = g_hwc;
+  const uint32_t c = idx ? (idx - 1) / kWChunk : 0u;
+  const uint64_t t = ((uint64_t)key * G::kPos + pos) * G::kChunks + c;
+  auto it = s.chunks.find(t);
+  if (it == s.chunks.end()) {
+    WCombFillTarget ft;
+    if (!wcomb_fill_target<W>(ft, t, s.nkeys) || ft.key != key || ft.pos != pos || ft.chunk != c) return nullptr;
+    std::vector<uint32_t> buf((size_t)(kWChunk + 2) * kWStride, kFillWord), tmp(kWChunk * 10);
+    wcomb_fill<W>(buf.data() + kWStride, tmp.data(), s.bases.data() + ((size_t)ft.key * G::kPos + ft.pos) * 40, ft.chunk);
+    it = s.chunks.emplace(t, std::move(buf)).first;
+  }
+  return it->second.data() + (size_t)(idx - kWChunk * c) * kWStride;
+}
+}  // namespace
+
+extern "C" {
+int nthb_wcomb_guard(uint32_t* out1);
+int nthb_wcomb_build(int bits, uint32_t nkeys, const uint32_t* enc8, int negate, uint32_t batch, uint32_t* meta_out) {
+  if (!ntp::wcomb_build_args_ok(bits, nkeys, negate, batch)) return 1;
+  int rc = 1;
+  ntp::wcomb_width(bits, [&](auto w) { rc = host_wcomb_build<decltype(w)::value>(nkeys, enc8, negate, batch, meta_out); });
+  if (rc) g_hwc.clear();
+  return rc;
+}
+int nthb_wcomb_free() {
+  uint32_t intact = 0;
+  if (!g_hwc.table.empty() && nthb_wcomb_guard(&intact) == 0 && intact) g_hwc_kept.push_back(std::move(g_hwc));
+  ntp::wcomb_width(g_hwc.bits, [&](auto w) { host_combs<decltype(w)::value>().clear(); });
+  g_hwc.clear();
+  return 0;
+}
+int nthb_wcomb_guard(uint32_t* out1) {
+  if (!g_hwc.bits) return 1;
+  *out1 = g_hwc.table.empty() || words_intact(g_hwc.table.data() + g_hwc.table.size() - kGuardWords, kGuardWords);
+  return 0;
+}
+int nthb_wcomb_digits(int bits, uint64_t n, const uint32_t* x8, uint32_t* out) {
+  const bool ok = ntp::wcomb_width(bits, [&](auto w) {
+    for (uint64_t i = 0; i < n; ++i) ntp::item_wcomb_digits<decltype(w)::value>(i, x8, out);
+  });
+  return ok ? 0 : 1;
+}
+int nthb_wcomb_entries(uint64_t n, const uint32_t* key, const uint32_t* pos, const uint32_t* idx, uint32_t* out32) {
+  int rc = 1;
+  ntp::wcomb_width(g_hwc.bits, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    using G = CombGeom<W>;
+    if (!ntp::wcomb_entry_args_ok<W>(n, g_hwc.nkeys, key, pos, idx)) return;
+    rc = 0;
+    for (uint64_t i = 0; i < n && !rc; ++i) {
+      if (!g_hwc.table.empty()) {
+        ntp::item_wcomb_entry(i, HostTabComb<W>{g_hwc.table.data() + (size_t)key[i] * G::kWordsPerPoint}, pos[i], idx[i],
+                              out32);
+        continue;
+      }
+      const uint32_t* e = idx[i] == ntp::kWcCorrIdx ? g_hwc.corr.data() + (size_t)key[i] * kWStride
+                                                    : host_chunk_entry<W>(key[i], pos[i], idx[i]);
+      if (!e) rc = 3;
+      else std::memcpy(out32 + 32 * i, e, 4 * kWStride);
+    }
+  });
+  return rc;
+}
+int nthb_wcomb_acc(uint64_t n, const uint32_t* key, const uint32_t* x8, const uint32_t* flags, const uint32_t* start_enc8,
+                   uint32_t* out_enc8) {
+  int rc = 1;
+  ntp::wcomb_width(g_hwc.bits, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    if (!ntp::wcomb_acc_args_ok<W>(n, g_hwc.nkeys, key, x8, flags)) return;
+    rc = 0;
+    std::vector<uint32_t> twin(g_hwc.table.empty() ? 0 : 8 * n);
+    for (uint64_t i = 0; i < n; ++i) {
+      ntp::item_wcomb_acc(i, HostCombRef<HostWComb<W>>{&host_combs<W>()[key[i]]}, x8, flags, start_enc8, out_enc8);
+      if (g_hwc.table.empty()) continue;
+      ntp::item_wcomb_acc(i, HostTabComb<W>{g_hwc.table.data() + (size_t)key[i] * CombGeom<W>::kWordsPerPoint}, x8, flags,
+                          start_enc8, twin.data());
+      if (std::memcmp(twin.data() + 8 * i, out_enc8 + 8 * i, 32) != 0) rc = 2;
+    }
+  });
+  return rc;
+}
+int nthb_key_comb_sum(uint64_t n, const uint32_t* key, const uint32_t* meta, const uint32_t* k8, uint32_t* out_enc8) {
+  int rc = 1;
+  ntp::wcomb_width(g_hwc.bits, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    if (!ntp::key_comb_args_ok<W>(n, g_hwc.nkeys, key, k8)) return;
+    rc = 0;
+    std::vector<uint32_t> twin(g_hwc.table.empty() ? 0 : 8 * n);
+    for (uint64_t i = 0; i < n; ++i) {
+      ntp::item_key_comb_sum(i, HostCombRef<HostWComb<W>>{&host_combs<W>()[key[i]]}, meta, k8, out_enc8);
+      if (g_hwc.table.empty()) continue;
+      ntp::item_key_comb_sum(i, HostTabComb<W>{g_hwc.table.data() + (size_t)key[i] * CombGeom<W>::kWordsPerPoint}, meta, k8,
+                             twin.data());
+      if (std::memcmp(twin.data() + 8 * i, out_enc8 + 8 * i, 32) != 0) rc = 2;
+    }
+  });
+  return rc;
+}
+// wcomb_fill_target of n threads t of a fill launch over nkeys keys: out = live, key, pos,
+// chunk, dst, tmp (6 words per thread); geom = kPos, kChunks, kEntries, kWordsPerPoint,
+// kCorrWord, then comb_size(bits, 0 .. 3)
+int nth_wcomb_fill_targets(int bits, uint32_t nkeys, uint64_t n, const uint64_t* t, uint64_t* out, uint64_t* geom) {
+  const bool ok = ntp::wcomb_width(bits, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    using G = CombGeom<W>;
+    const uint64_t g[9] = {G::kPos, G::kChunks, G::kEntries, G::kWordsPerPoint, G::kCorrWord, comb_size<W>(0),
+                           comb_size<W>(1), comb_size<W>(2), comb_size<W>(3)};
+    std::memcpy(geom, g, sizeof g);
+    for (uint64_t i = 0; i < n; ++i) {
+      WCombFillTarget ft{0, 0, 0, 0, 0};
+      const bool live = wcomb_fill_target<W>(ft, t[i], nkeys);
+      const uint64_t o[6] = {live, ft.key, ft.pos, ft.chunk, ft.dst, ft.tmp};
+      std::memcpy(out + 6 * i, o, sizeof o);
+    }
+  });
+  return ok ? 0 : 1;
+}
+// the offsets of the fill launch of keys k0 .. of a build: out = nkeys, threads, bases_off, comb_off
+int nth_wcomb_fill_launch(int bits, uint32_t k0, uint32_t total, uint32_t batch, uint64_t* out) {
+  const bool ok = ntp::wcomb_width(bits, [&](auto w) {
+    const WCombFillLaunch fl = wcomb_fill_launch<decltype(w)::value>(k0, total, batch);
+    const uint64_t o[4] = {fl.nkeys, fl.threads, fl.bases_off, fl.comb_off};
+    std::memcpy(out, o, sizeof o);
+  });
+  return ok ? 0 : 1;
 }
 }

@@ -6,8 +6,11 @@
 // header function under test; no arithmetic lives here.
 // Field elements are 10 limbs, encodings and scalars 8 little-endian words.
 #pragma once
+#include <type_traits>
+
 #include "../../narwhal-tusk_amd/csrc/ed25519_ops.hpp"
 #include "../../narwhal-tusk_amd/csrc/fe_inv_vt.hpp"
+#include "../../narwhal-tusk_amd/csrc/wcomb_build.hpp"
 
 namespace ntp {
 using namespace nt;
@@ -293,6 +296,174 @@ NT_HD NT_INLINE void item_ladder_uv3(size_t i, const uint32_t* kidx, const uint3
   ge_cp_to_p2(p, t);
   ge_tobytes_w(o, p);
   if (write) st_w<8>(out8, i, o);
+}
+
+// ---- the wide combs (ed25519_ops.hpp wcomb_*, wcomb_build.hpp): digits, table entries, sums.
+// A comb type here is the product's WideComb<W> (device), or a host type with the same
+// members: kBits, base, load, load_corr.
+constexpr uint32_t kWcCorrIdx = 0xffffffffu;  // "the [L]P entry" where an entry index is expected
+constexpr uint32_t kWcMaxKeys = 8;            // keys of one probe comb set
+constexpr size_t kWcGuardBytes = 8192;        // the pattern that follows the combs
+constexpr int kWcFill = 0xA5;                 // ... and fills them before the build
+constexpr int kWcMaxLoads = 17;               // kPos + 1 of the narrowest comb: wcomb_acc's loads
+constexpr int kWcDigitWords = 64;             // words per item of the digits probe
+
+// bits -> f(std::integral_constant<int, W>); false: not one of the five widths
+template <class F>
+inline bool wcomb_width(int bits, F&& f) {
+  switch (bits) {
+    case kKeyCombNarrow: f(std::integral_constant<int, kKeyCombNarrow>{}); return true;
+    case kKeyCombMid: f(std::integral_constant<int, kKeyCombMid>{}); return true;
+    case kKeyCombWide: f(std::integral_constant<int, kKeyCombWide>{}); return true;
+    case kKeyCombReduced: f(std::integral_constant<int, kKeyCombReduced>{}); return true;
+    case kBCombBits: f(std::integral_constant<int, kBCombBits>{}); return true;
+    default: return false;
+  }
+}
+
+// The digits wcomb_acc takes from x, in its order: digit j < kPos belongs to position j (the
+// last one of a reduced comb unsigned), digit kPos is the one behind the last round's reload.
+template <int W>
+NT_HD NT_INLINE void wcomb_schedule(int32_t dg[kWcMaxLoads], const uint32_t x[8]) {
+  constexpr int P = CombGeom<W>::kPos;
+  uint32_t d[8], carry = 0;
+#pragma unroll
+  for (int m = 0; m < 8; ++m) d[m] = x[m];
+  for (int j = 0; j <= P; ++j) dg[j] = wcomb_digit<W>(d, carry, CombGeom<W>::kReduced && j == P - 1);
+}
+// every table index wcomb_acc forms for x lies inside a position's kEntries
+template <int W>
+inline bool wcomb_scalar_ok(const uint32_t x[8]) {
+  int32_t dg[kWcMaxLoads];
+  wcomb_schedule<W>(dg, x);
+  for (int j = 0; j <= CombGeom<W>::kPos; ++j)
+    if ((dg[j] < 0 ? -dg[j] : dg[j]) >= CombGeom<W>::kEntries) return false;
+  return true;
+}
+// A comb that reads nothing: it notes (position, index) of every load wcomb_acc issues, in
+// order, at rec[1 ..] and their count at rec[0], and hands back the identity.
+template <int W>
+struct RecordingComb {
+  static constexpr int kBits = W;
+  uint32_t* rec;
+  NT_HD NT_INLINE void load(uint32_t pos, uint32_t idx, ge_niels& q) const {
+    const uint32_t c = rec[0];
+    if (c < (uint32_t)kWcMaxLoads) {
+      rec[1 + 2 * c] = pos;
+      rec[2 + 2 * c] = idx;
+    }
+    rec[0] = c + 1;
+    ge_niels_0(q);
+  }
+  NT_HD NT_INLINE void load_corr(ge_niels& q) const { ge_niels_0(q); }
+};
+// out (kWcDigitWords per item): words 0 .. kPos the schedule's signed digits; word 17 the
+// number of loads wcomb_acc itself issued for x and from word 18 on their (position, index)
+template <int W>
+NT_HD NT_INLINE void item_wcomb_digits(size_t i, const uint32_t* x8, uint32_t* out) {
+  uint32_t x[8];
+  ld_w<8>(x, x8, i);
+  uint32_t* o = out + (size_t)kWcDigitWords * i;
+  int32_t dg[kWcMaxLoads];
+  wcomb_schedule<W>(dg, x);
+  for (int j = 0; j < kWcDigitWords; ++j) o[j] = 0;
+  for (int j = 0; j <= CombGeom<W>::kPos; ++j) o[j] = (uint32_t)dg[j];
+  ge_p3 acc;
+  wcomb_acc<RecordingComb<W>, true>(acc, x, RecordingComb<W>{o + kWcMaxLoads});
+}
+// entry (pos, idx) of the comb through load (idx = kWcCorrIdx: load_corr): the 30 limbs, then
+// words 30 and 31 of the entry as they lie in memory
+template <class Comb>
+NT_HD NT_INLINE void item_wcomb_entry(size_t i, const Comb& wc, uint32_t pos, uint32_t idx, uint32_t* out32) {
+  using G = CombGeom<Comb::kBits>;
+  ge_niels q;
+  size_t word;
+  if (idx == kWcCorrIdx) {
+    wc.load_corr(q);
+    word = G::kCorrWord;
+  } else {
+    wc.load(pos, idx, q);
+    word = ((size_t)pos * G::kEntries + idx) * kWStride;
+  }
+  uint32_t* o = out32 + 32 * i;
+#pragma unroll
+  for (int l = 0; l < 10; ++l) { o[l] = q.ypx.v[l]; o[10 + l] = q.ymx.v[l]; o[20 + l] = q.xy2d.v[l]; }
+  o[30] = wc.base[word + 30];
+  o[31] = wc.base[word + 31];
+}
+NT_HD NT_INLINE void st_point(uint32_t* out8, size_t i, const ge_p3& P) {
+  ge_p2 p;
+  ge_p3_to_p2(p, P);
+  uint32_t o[8];
+  ge_tobytes_w(o, p);
+  st_w<8>(out8, i, o);
+}
+// out = start + [+-x]P through wcomb_acc; flags bit 0: kFromIdentity (start unused), bit 1:
+// neg_all.  A start that does not decode counts as the identity.
+template <class Comb>
+NT_HD NT_INLINE void item_wcomb_acc(size_t i, const Comb& wc, const uint32_t* x8, const uint32_t* flags,
+                                    const uint32_t* start8, uint32_t* out8) {
+  uint32_t x[8], s[8];
+  ld_w<8>(x, x8, i);
+  ld_w<8>(s, start8, i);
+  const uint32_t neg = (flags[i] >> 1) & 1u;
+  ge_p3 acc;
+  if (flags[i] & 1u) {
+    wcomb_acc<Comb, true>(acc, x, wc, neg);
+  } else {
+    if (!ge_frombytes_w(acc, s)) ge_p3_0(acc);
+    wcomb_acc<Comb, false>(acc, x, wc, neg);
+  }
+  st_point(out8, i, acc);
+}
+// [k](-A) as cached_point forms it from the key's comb: key_comb_sum
+template <class Comb>
+NT_HD NT_INLINE void item_key_comb_sum(size_t i, const Comb& wc, const uint32_t* meta, const uint32_t* k8,
+                                       uint32_t* out8) {
+  uint32_t k[8];
+  ld_w<8>(k, k8, i);
+  ge_p3 acc;
+  key_comb_sum(acc, k, meta[i], wc);
+  st_point(out8, i, acc);
+}
+// the scalar key_comb_sum hands to wcomb_acc keeps inside the table
+template <int W>
+inline bool key_comb_scalar_ok(const uint32_t k8[8]) {
+  uint32_t k[8];
+  for (int m = 0; m < 8; ++m) k[m] = k8[m];
+  if (CombGeom<W>::kReduced) (void)sc_reduce_half(k);
+  return wcomb_scalar_ok<W>(k);
+}
+// the argument checks of the comb entry points, on the host before anything runs
+template <int W>
+inline bool wcomb_entry_args_ok(uint64_t n, uint32_t nkeys, const uint32_t* key, const uint32_t* pos,
+                                const uint32_t* idx) {
+  using G = CombGeom<W>;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (key[i] >= nkeys) return false;
+    if (idx[i] == kWcCorrIdx ? !G::kReduced : (pos[i] >= (uint32_t)G::kPos || idx[i] >= (uint32_t)G::kEntries)) return false;
+  }
+  return true;
+}
+template <int W>
+inline bool wcomb_acc_args_ok(uint64_t n, uint32_t nkeys, const uint32_t* key, const uint32_t* x8,
+                              const uint32_t* flags) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (key[i] >= nkeys || flags[i] > 3u || !wcomb_scalar_ok<W>(x8 + 8 * i)) return false;
+  return true;
+}
+template <int W>
+inline bool key_comb_args_ok(uint64_t n, uint32_t nkeys, const uint32_t* key, const uint32_t* k8) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (key[i] >= nkeys || !key_comb_scalar_ok<W>(k8 + 8 * i)) return false;
+  return true;
+}
+// what a comb set may be: one of the five widths; the 24-bit comb for one point, not negated
+// (the product builds it for B alone); at most kWcMaxKeys keys; a batch of at least one key
+inline bool wcomb_build_args_ok(int bits, uint32_t nkeys, int negate, uint32_t batch) {
+  if (!wcomb_width(bits, [](auto) {})) return false;
+  if (nkeys < 1 || nkeys > kWcMaxKeys || batch < 1) return false;
+  return bits != kBCombBits || (nkeys == 1 && !negate);
 }
 
 }  // namespace ntp

@@ -8,7 +8,13 @@ wave_max), scalars with huge partial quotients through the v_rcp_f64 Lehmer
 quotient, messages at every byte alignment -- and, behind the key-table cache, the
 unbalanced lattice vector with huge quotients at its own stop (2^191.5), the
 product's DevKTab filled and read back point by point, and the three-table ladder
-with chosen digits and window counts.  tests/test_host_arith.py runs the
+with chosen digits and window counts.  The wide combs behind every fixed-point
+multiplication ([s]B, [k](-A)) are built here by the product's own wcomb_build at
+all five digit widths and read back through WideComb::load entry by entry -- entry
+2^(W-1), entry 0, the reduced comb's extra chunk and its [L](-A) entry, a short last
+fill batch -- with the digit schedule and the sums at chosen scalars: a carry
+through every position, a zero first digit from the identity, waves in which only
+some lanes owe the reduced comb's correction.  tests/test_host_arith.py runs the
 same checks on the host build.  Nothing is compiled here: a missing or stale
 probe library fails at once.
 """
@@ -98,3 +104,26 @@ def test_key_table_entries_and_cached_points(dev):
 
 def test_three_table_ladder_lane_mixed_window_counts(dev, host):
     C.check_ladder3(dev, H.host_unbalanced, H.host_halfsize)
+
+
+@pytest.mark.parametrize("bits", C.COMB_WIDTHS)
+def test_wide_comb_tables(dev, bits):
+    print("comb entries compared at %d bits: %d" % (bits, C.check_wcomb_tables(dev, bits)))
+
+
+@pytest.mark.parametrize("bits", C.COMB_WIDTHS)
+def test_wide_comb_digits(dev, bits):
+    print("digit vectors compared at %d bits: %d" % (bits, C.check_wcomb_digits(dev, bits)))
+
+
+@pytest.mark.parametrize("bits", C.COMB_WIDTHS)
+def test_wide_comb_sums(dev, bits):
+    print("comb sums compared at %d bits: %d" % (bits, C.check_wcomb_acc(dev, bits)))
+
+
+def test_key_comb_sum_lane_mixed_corrections(dev):
+    print("key comb sums compared per width: %d" % C.check_key_comb_sum(dev))
+
+
+def test_wide_comb_entry_points_refuse_bad_arguments(dev):
+    print("comb calls refused: %d" % C.check_wcomb_refusals(dev))

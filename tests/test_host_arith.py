@@ -110,6 +110,99 @@ def test_three_table_ladder_lane_mixed_window_counts(host):
     C.check_ladder3(host, H.host_unbalanced, H.host_halfsize)
 
 
+@pytest.mark.parametrize("bits", C.COMB_WIDTHS)
+def test_wide_comb_tables(host, bits):
+    """wcomb_key_bases + wcomb_fill through wcomb_fill_target at all five widths (16 bits: whole
+    combs, built batch by batch as wcomb_build launches them)"""
+    print("comb entries compared at %d bits: %d" % (bits, C.check_wcomb_tables(host, bits)))
+
+
+@pytest.mark.parametrize("bits", C.COMB_WIDTHS)
+def test_wide_comb_digits(host, bits):
+    print("digit vectors compared at %d bits: %d" % (bits, C.check_wcomb_digits(host, bits)))
+
+
+@pytest.mark.parametrize("bits", C.COMB_WIDTHS)
+def test_wide_comb_sums(host, bits):
+    print("comb sums compared at %d bits: %d" % (bits, C.check_wcomb_acc(host, bits)))
+
+
+def test_key_comb_sum_lane_mixed_corrections(host):
+    print("key comb sums compared per width: %d" % C.check_key_comb_sum(host))
+
+
+def test_wide_comb_entry_points_refuse_bad_arguments(host):
+    print("comb calls refused: %d" % C.check_wcomb_refusals(host))
+
+
+def _fill_targets(bits, nkeys, t):
+    """wcomb_fill_target of the threads t: (live, key, pos, chunk, dst, tmp) columns and the width's
+    geometry (kPos, kChunks, kEntries, kWordsPerPoint, kCorrWord, comb / bases / tmp bytes per key, batch)"""
+    import ctypes
+    t = np.ascontiguousarray(t, np.uint64)
+    out, geom = np.zeros((len(t), 6), np.uint64), np.zeros(9, np.uint64)
+    rc = H.load().nth_wcomb_fill_targets(bits, ctypes.c_uint32(nkeys), ctypes.c_uint64(len(t)), C._p(t), C._p(out), C._p(geom))
+    assert rc == 0
+    return out.astype(np.int64), [int(g) for g in geom]
+
+
+@pytest.mark.parametrize("bits", C.COMB_WIDTHS)
+def test_wcomb_fill_target_map(bits):
+    """The thread -> (key, position, chunk) map of k_wcomb_fill for 1, 2 and 5 keys, every thread of
+    the grid (24 bits: every 61st, and the first and last thread of every key and position): key,
+    position and chunk invert to t; the chunks' 64-entry destinations are disjoint, cover each
+    position of each key exactly from entry 1 on (entry 0 is chunk 0's extra write) and stay inside
+    the keys' combs; the tmp slices are disjoint and inside the product's tmp size for the batch;
+    threads past the work are dead.  Then the per-batch offsets of wcomb_build's launches."""
+    import ctypes
+    npos, chunks, entries = C.comb_geom(bits)
+    per_key = npos * chunks
+    for nkeys in (1, 2, 5):
+        threads = per_key * nkeys
+        if bits == C.COMB_B:
+            firsts = np.arange(0, threads, chunks)
+            t = np.unique(np.concatenate([np.arange(0, threads, 61), firsts, firsts + chunks - 1]))
+        else:
+            t = np.arange(threads)
+        t = np.concatenate([t, threads + np.array([0, 1, 63, per_key, 1 << 33])]).astype(np.uint64)
+        got, geom = _fill_targets(bits, nkeys, t)
+        assert geom[:3] == [npos, chunks, entries]
+        wpp, corr_word, comb_bytes, bases_bytes, tmp_bytes, batch = geom[3:]
+        assert corr_word == npos * entries * 32 and wpp == corr_word + (32 if bits == C.COMB_REDUCED else 0)
+        assert comb_bytes == 4 * wpp and bases_bytes == 160 * npos and tmp_bytes == per_key * 2560
+        assert batch == max(1, (128 << 10) // per_key)
+        live, key, pos, chunk, dst, tmp = got.T
+        ti = t.astype(np.int64)
+        assert np.array_equal(live != 0, ti < threads)
+        m = live != 0
+        ti, key, pos, chunk, dst, tmp = ti[m], key[m], pos[m], chunk[m], dst[m], tmp[m]
+        assert np.all((key < nkeys) & (pos < npos) & (chunk < chunks))
+        assert np.array_equal((key * npos + pos) * chunks + chunk, ti)
+        # a chunk writes entries [first, first + 64) of its position; chunk 0 also the entry before
+        assert np.all(dst % 32 == 0)
+        first = dst // 32 - key * (wpp // 32) - pos * entries       # entry index inside the position
+        assert np.array_equal(first, 1 + 64 * chunk)
+        assert np.all(first + 64 <= entries) and first.min() == 1 and (first + 64).max() == entries
+        if bits != C.COMB_B:                                        # every thread: disjoint, exact cover
+            order = np.argsort(dst)
+            assert np.all(np.diff(dst[order]) >= 64 * 32)
+            assert len(np.unique(key * npos + pos)) == nkeys * npos and len(dst) == nkeys * npos * chunks
+        assert dst.max() + 64 * 32 <= wpp * nkeys - (32 if bits == C.COMB_REDUCED else 0)
+        assert np.all(tmp % 640 == 0) and len(np.unique(tmp)) == len(tmp)
+        assert tmp.max() + 640 <= tmp_bytes // 4 * nkeys
+    out = np.zeros(4, np.uint64)
+    for total, batch in ((5, 2), (1, 1), (5, 16), (2, 2), (5, 1)):
+        k0, seen = 0, []
+        while k0 < total:
+            assert H.load().nth_wcomb_fill_launch(bits, ctypes.c_uint32(k0), ctypes.c_uint32(total), ctypes.c_uint32(batch), C._p(out)) == 0
+            nk, threads, bases_off, comb_off = (int(x) for x in out)
+            assert 1 <= nk <= batch and nk == min(batch, total - k0) and threads == nk * per_key
+            assert bases_off == k0 * npos * 40 and comb_off == k0 * wpp
+            seen.append(nk)
+            k0 += batch
+        assert sum(seen) == total and len(seen) == -(-total // batch)
+
+
 def test_device_probe_exports_every_entry():
     """tests/cpp/build/libntprobe.so (the gfx950 build of the same item functions)
     exports one ntp_* entry point per check; loading it needs no GPU"""
@@ -119,7 +212,7 @@ def test_device_probe_exports_every_entry():
     lib = _devprobe.load()
     for sym in _devprobe.EXPORTS:
         getattr(lib, sym)
-    assert len(_devprobe.EXPORTS) == 21
+    assert len(_devprobe.EXPORTS) == 28
 
 
 def test_sha512_host_build():
