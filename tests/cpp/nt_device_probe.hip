@@ -14,6 +14,8 @@
 // schedule), k_wcomb_entries (WideComb::load / load_corr), k_wcomb_acc, k_key_comb_sum --
 // the last three over combs that ntp_wcomb_build makes with the product's own
 // k_wcomb_bases / k_wcomb_fill through wcomb_build<W> (csrc/wcomb_build.hpp).
+// ntp_key_sort runs the product's counting sort (csrc/key_sort.hpp launch_key_sort: k_key_hist,
+// k_key_scatter) and hands back the permutation a key-cache launch would walk.
 // Never linked into libntcrypto.so.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +23,7 @@
 #include <cstring>
 
 #include "../../narwhal-tusk_amd/csrc/kernels_common.hpp"
+#include "../../narwhal-tusk_amd/csrc/key_sort.hpp"
 #include "nt_probe_items.hpp"
 
 using namespace nt;
@@ -568,5 +571,23 @@ int ntp_key_comb_sum(uint64_t n, const uint32_t* key, const uint32_t* meta, cons
   dout.back(out_enc8, 32 * n);
   return (int)err;
 }
+
+// perm_out[0 .. n) = the key-grouped order of key[0 .. n) (slot -> signature), as
+// launch_verify_keyset gets it: bucket lines zeroed, then launch_key_sort.  Device-only
+// (no host twin: the sort is two kernels, not a device function of the headers).
+int ntp_key_sort(uint64_t n, const uint32_t* key, int mixed, uint32_t nkeys, uint32_t* perm_out) {
+  NTP_BEGIN
+  if (nkeys + 1 > kSortBuckets || n > 0xFFFFFFFFull) return (int)hipErrorInvalidValue;
+  const size_t line_bytes = 4ull * kCtrStride * (nkeys + 1);
+  Dev dkey(&err, key, 4 * n), dlines(&err, nullptr, line_bytes), dperm(&err, nullptr, 4 * n);
+  if (err == hipSuccess) err = hipMemset(dlines.p, 0, line_bytes);
+  if (err == hipSuccess) err = hipMemset(dperm.p, 0xFF, 4 * n);
+  if (err == hipSuccess) err = launch_key_sort(dkey.as<uint32_t>(), n, mixed, nkeys, dlines.as<uint32_t>(),
+                                              dperm.as<uint32_t>(), 0);
+  finish(&err);
+  dperm.back(perm_out, 4 * n);
+  return (int)err;
+}
+
 
 }  // extern "C"

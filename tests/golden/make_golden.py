@@ -22,7 +22,7 @@ crate sources), so these independent implementations are the pin.
 Run in the development container (needs /opt/conda/lib/libsodium.so.23):
     python tests/golden/make_golden.py
 Outputs: sha512_vectors.json, fixtures_reference.json, ed25519_corpus.npz,
-         ed25519_corpus.json, batch_groups.npz
+         ed25519_corpus.json, batch_groups.npz, torsion_votes.npz
 """
 import ctypes
 import hashlib
@@ -607,6 +607,131 @@ def build_groups(corpus_entries):
                 expect=np.array(expect, np.uint8), deterministic=np.array(det, np.uint8))
 
 
+# --------------------------------------------------------------------------
+# 5) votes under torsion keys: 12 keys x 40 certificate digests
+# --------------------------------------------------------------------------
+HALF_L = (L - 1) // 2
+TORSION_VOTE_KINDS = ["prime", "mixed", "small"]
+TORSION_MIN_PER_BRANCH = 8
+
+
+def torsion_vote_keys(g):
+    """(kind, torsion index, pk, secret) of the 12 keys: seven mixed-order keys
+    A = aB + TORSION[t], t = 1..7; two keys of order 8 (TORSION[1], TORSION[3]);
+    three prime-order controls (libsodium keypairs)."""
+    keys = []
+    for t in range(1, 8):
+        a = g.scalar()
+        keys.append((1, t, encode(padd(pmul(a, BASE), TORSION[t])), a))
+    for t in (1, 3):
+        assert not is_ident(pmul(4, TORSION[t]))
+        keys.append((2, t, encode(TORSION[t]), None))
+    for _ in range(3):
+        pk, sk = sodium_keypair(g.bytes(32))
+        keys.append((0, 0, pk, sk))
+    return keys
+
+
+def torsion_vote_sign(g, key, m):
+    """A signature the strict rule (mixed, prime) or the cofactorless equation
+    (small order) accepts, built as the corpus categories mixed_A_valid and
+    small_A_R_exact build theirs."""
+    kind, t, pk, sec = key
+    if kind == 0:
+        return sodium_sign(sec, m)
+    if kind == 1:
+        while True:  # mixed_A_valid: R = [r]B + T_j with T_j + [k]T_t = 0, s = r + k a
+            r = g.scalar()
+            for j in range(8):
+                Rj = encode(padd(pmul(r, BASE), TORSION[j]))
+                s = (r + hram(Rj, pk, m) * sec) % L
+                cand = Rj + s.to_bytes(32, "little")
+                if model_strict(pk, cand, m):
+                    return cand
+    # small_A_R_exact: R = T_j with j + k t = 0 mod 8 and s = 0; where no j of
+    # the eight fits this digest, the same equation with R = [r]B + T_j, s = r
+    r = 0
+    while True:
+        rB = pmul(r, BASE)
+        for j in range(8):
+            Rj = encode(padd(rB, TORSION[j]))
+            if (j + hram(Rj, pk, m) * t) % 8 == 0:
+                return Rj + r.to_bytes(32, "little")
+        r = g.scalar()
+
+
+def build_torsion_votes(ndigests=40, seed=b"nt-torsion-votes-3"):
+    """Entry (key, g) at row 40 * key + g: key's vote on certificate digest g.
+    A seeded ~10 % are spoiled (one bit of s flipped, or R shifted by a torsion
+    point); every label comes from the model, not from how the entry was made."""
+    g = Gen(seed)
+    keys = torsion_vote_keys(g)
+    digests = [g.bytes(32) for _ in range(ndigests)]
+    rows = []
+    for ki, key in enumerate(keys):
+        for gi, m in enumerate(digests):
+            sig = torsion_vote_sign(g, key, m)
+            pick = g.bytes(4)
+            if pick[0] < 26:  # 26 / 256 ~ 10 %
+                if pick[1] & 1:
+                    s = int.from_bytes(sig[32:], "little") ^ (1 << pick[2])
+                    sig = sig[:32] + s.to_bytes(32, "little")
+                else:
+                    sig = encode(padd(decode(sig[:32]), TORSION[1 + pick[2] % 7])) + sig[32:]
+            rows.append((ki, gi, key[2], sig, m))
+    n = len(rows)
+    out = dict(pk=np.zeros((n, 32), np.uint8), sig=np.zeros((n, 64), np.uint8),
+               msg32=np.frombuffer(b"".join(digests), np.uint8).reshape(-1, 32).copy(),
+               group=np.zeros(n, np.uint32), key=np.zeros(n, np.uint32), strict=np.zeros(n, np.uint8),
+               batch_rule=np.zeros(n, np.uint8), k=np.zeros((n, 32), np.uint8),
+               keys=np.frombuffer(b"".join(k[2] for k in keys), np.uint8).reshape(-1, 32).copy(),
+               kind=np.array([k[0] for k in keys], np.uint8))
+    for i, (ki, gi, pk, sig, m) in enumerate(rows):
+        out["pk"][i] = np.frombuffer(pk, np.uint8)
+        out["sig"][i] = np.frombuffer(sig, np.uint8)
+        out["group"][i], out["key"][i] = gi, ki
+        out["strict"][i] = model_strict(pk, sig, m)
+        out["batch_rule"][i] = model_batch_entry(pk, sig, m)[0]
+        out["k"][i] = np.frombuffer(hram(sig[:32], pk, m).to_bytes(32, "little"), np.uint8)
+        if keys[ki][0] == 0 and bool(out["strict"][i]) != sodium_verify(pk, sig, m):
+            raise SystemExit("libsodium / dalek-model disagreement on torsion vote %d" % i)
+    return out
+
+
+def torsion_branch_counts(tv):
+    """Per key: (batch-rule-accepted entries with k <= (L-1)/2, with k above).
+    The two branches of the reduced-scalar comb; only the second owes [L](-A)."""
+    k = [int.from_bytes(x.tobytes(), "little") for x in tv["k"]]
+    out = []
+    for ki in range(len(tv["keys"])):
+        sel = [i for i in np.flatnonzero(tv["key"] == ki) if tv["batch_rule"][i]]
+        out.append((sum(k[i] <= HALF_L for i in sel), sum(k[i] > HALF_L for i in sel)))
+    return out
+
+
+def write_torsion_votes(path):
+    nd = 40
+    while True:
+        tv = build_torsion_votes(nd)
+        counts = torsion_branch_counts(tv)
+        spoiled = [int((tv["batch_rule"][tv["key"] == ki] == 0).sum()) for ki in range(len(counts))]
+        if min(spoiled) < 2:  # the seed was picked for this: no key whose wave accepts everywhere
+            raise SystemExit("torsion votes: a key has fewer than 2 rejected entries: %r" % spoiled)
+        if all(min(c) >= TORSION_MIN_PER_BRANCH for c, kd in zip(counts, tv["kind"]) if kd):
+            break
+        nd += 8  # more digests, never a lower bound
+        if nd > 120:
+            raise SystemExit("torsion votes: a key lacks %d accepted entries per branch: %r"
+                             % (TORSION_MIN_PER_BRANCH, counts))
+    print("torsion_votes.npz: %d keys x %d digests; accepted entries with k <= (L-1)/2 | k > (L-1)/2" % (len(counts), nd))
+    for ki, (lo, hi) in enumerate(counts):
+        sel = tv["key"] == ki
+        print("  key %2d %-5s  low %2d  high %2d  strict-valid %2d  batch-valid %2d" % (
+            ki, TORSION_VOTE_KINDS[int(tv["kind"][ki])], lo, hi, int(tv["strict"][sel].sum()),
+            int(tv["batch_rule"][sel].sum())))
+    np.savez_compressed(path, **tv)
+
+
 def main():
     assert encode(BASE).hex() == "58" + "66" * 31, "base point encoding"
     with open(os.path.join(HERE, "sha512_vectors.json"), "w") as f:
@@ -633,6 +758,7 @@ def main():
     grp = build_groups(entries)
     np.savez_compressed(os.path.join(HERE, "batch_groups.npz"), **grp)
     print("batch_groups.npz: %d groups, %d signatures" % (len(grp["cnt"]), len(grp["pk"])))
+    write_torsion_votes(os.path.join(HERE, "torsion_votes.npz"))
 
 
 if __name__ == "__main__":

@@ -302,6 +302,26 @@ def test_keyset_committee_random_vs_oracle(be, oracle):
     assert got.sum() == (~flip).sum()
     flags = [ks.flags(i) for i in range(nk)]
     assert all(f == 1 for f in flags)
+    # certificates at committee scale on the same set (the default width: 21 bits): 1,000
+    # certificates of 67 votes on random digests, 67,000 signatures in one key-grouped, fused
+    # launch, a seeded 1 % of the votes corrupted; against the oracle
+    assert ks.info()[0] == 21
+    G, q = 1000, 67
+    digests = rng.integers(0, 256, (G, 32), dtype=np.uint8)
+    voters = np.concatenate([rng.permutation(nk)[:q] for _ in range(G)]).astype(np.uint32)
+    V = G * q
+    first = np.arange(G, dtype=np.uint64) * q
+    cnt = np.full(G, q, np.uint32)
+    _, vsig = be.sign_batch(seeds[voters], np.repeat(digests, q, axis=0).reshape(-1),
+                            np.arange(V, dtype=np.uint64) * 32, np.full(V, 32, np.uint64))
+    vsig = vsig.copy()
+    bad = rng.random(V) < 0.01
+    vsig[bad, rng.integers(0, 64, V)[bad]] ^= 1 << 3
+    gb, sb = ks.verify_batch_groups(voters, vsig, first, cnt, digests, with_sig_bits=True)
+    og, osb = oracle.verify_batch_groups(pks[voters], vsig, first, cnt, digests, nthreads=8)
+    assert np.array_equal(sb, osb.astype(bool)) and np.array_equal(gb, og.astype(bool))
+    assert np.array_equal(sb, ~bad)
+    assert int((~gb).sum()) == int(bad.reshape(G, q).any(axis=1).sum()) > 0
     ks.close()
 
 

@@ -6,9 +6,13 @@ raw 32-byte encodings.  Registered keys verify through the key-cache kernel,
 the others through the uncached kernel in the same call; the verdicts must be
 the corpus labels and the oracle's whichever way each key goes.
 
-Key combs at 16 bits (67 MB per key) unless a test says otherwise, so a few
-hundred corpus keys fit beside everything else; the kernel's arithmetic is
-the same at every width (test_gpu_parity.py::test_keyset_corpus)."""
+Key combs at 16 bits (67 MB per key) where a test registers a few hundred
+corpus keys, so that they fit beside everything else.  The kernel's arithmetic
+is NOT the same at every width: only the 21-bit reduced-scalar combs -- what a
+registry gets by default -- take k as k or k - L and owe a torsion key's
+[L](-A) entry.  The test_registry_default_width_* tests below run the registry
+with no width override over tests/golden/torsion_votes.npz (votes under
+mixed-order and order-8 keys), admissions at growing offsets included."""
 import os
 
 import numpy as np
@@ -281,3 +285,148 @@ def test_registry_concurrent_calls_during_admission(reg):
     reg.key_cache_sync()
     info = reg.key_cache_info()
     assert info["keys"] == nk and info["error"] == 0 and info["hits"] > 0, info
+
+
+# ------------------------------------------------------------------ the registry at its default width
+@pytest.fixture(scope="module")
+def tv():
+    import _torsion_votes as T
+    return T.load()
+
+
+@pytest.fixture(scope="module")
+def certs(tv):
+    import _torsion_votes as T
+    return T.certificates(tv)
+
+
+@pytest.fixture()
+def reg21(monkeypatch):
+    """A fresh context with a registry of capacity 16 and no width override:
+    21-bit reduced-scalar combs, 1.61 GB per admitted key."""
+    import ntcrypto
+    monkeypatch.delenv("NT_KEYSET_COMB_BITS", raising=False)
+    b = ntcrypto.Backend(device=0)
+    b.set_key_cache(16)
+    yield b
+    b.close()
+
+
+def _strict_of_keys(b, tv, keys):
+    """verify_strict over the entries of these keys: (verdicts, labels, hits and misses the call added)"""
+    sel = np.flatnonzero(np.isin(tv["key"], keys))
+    i0 = b.key_cache_info()
+    got = b.verify_strict(tv["pk"][sel], tv["sig"][sel], tv["msg32"].reshape(-1), tv["off"][sel], tv["len"][sel])
+    i1 = b.key_cache_info()
+    return got, tv["strict"][sel].astype(bool), i1["hits"] - i0["hits"], i1["misses"] - i0["misses"]
+
+
+def _plain_calls(b, tv, certs):
+    """verify_strict over all entries and verify_batch_groups over the certificates: the three
+    result arrays and each call's (hits, misses, signatures)"""
+    rows, first, cnt, msg32, _, _ = certs
+    i0 = b.key_cache_info()
+    st = b.verify_strict(tv["pk"], tv["sig"], tv["msg32"].reshape(-1), tv["off"], tv["len"])
+    i1 = b.key_cache_info()
+    gb, sb = b.verify_batch_groups(tv["pk"][rows], tv["sig"][rows], first, cnt, msg32, with_sig_bits=True)
+    i2 = b.key_cache_info()
+    counts = [(i1["hits"] - i0["hits"], i1["misses"] - i0["misses"], len(tv["pk"])),
+              (i2["hits"] - i1["hits"], i2["misses"] - i1["misses"], len(rows))]
+    return st, gb, sb, counts
+
+
+def test_registry_default_width_admissions(reg21, tv):
+    """Admissions one after another at 1.61 GB per key (registry.cpp build():
+    an admission's combs start at words * nk): 5 keys, then 4, then a call
+    that also offers a key that does not decode, then the last 3 on sight (a
+    groups call that holds them, nt_key_cache_sync).  After every step the
+    counters are what the step admitted, the width is 21 bits, and the strict
+    verdicts of the entries of EVERY key admitted so far -- through the key
+    cache: all hits -- equal the labels: a later admission must not disturb an
+    earlier key's comb."""
+    keys = tv["keys"]
+
+    def check(step, nkeys, refused):
+        info = reg21.key_cache_info()
+        print(step, info)
+        assert (info["keys"], info["refused"], info["pending"], info["error"], info["comb_bits"]) == \
+            (nkeys, refused, 0, 0, 21), (step, info)
+        got, want, hits, misses = _strict_of_keys(reg21, tv, np.arange(nkeys))
+        assert (hits, misses) == (len(want), 0), (step, hits, misses)
+        bad = np.flatnonzero(got != want)
+        assert len(bad) == 0, (step, bad[:16].tolist())
+
+    reg21.key_cache_add(keys[:5])
+    check("5 keys", 5, 0)
+    reg21.key_cache_add(keys[5:9])
+    check("then 4", 9, 0)
+    junk = np.zeros((1, 32), np.uint8)
+    junk[0, 0] = 2                                  # y = 2: not on the curve
+    reg21.key_cache_add(np.concatenate([keys[:1], junk, keys[8:9]]))
+    check("a key that does not decode", 9, 1)
+    sel = np.flatnonzero(tv["key"] >= 9)
+    gb = reg21.verify_batch_groups(tv["pk"][sel], tv["sig"][sel], np.arange(len(sel), dtype=np.uint64),
+                                   np.ones(len(sel), np.uint32), tv["msg32"][tv["group"][sel]])
+    assert np.array_equal(gb, tv["batch_rule"][sel].astype(bool))
+    reg21.key_cache_sync()
+    check("3 on sight", 12, 1)
+    assert reg21.key_cache_info()["admitted"] == 12
+
+
+def test_registry_default_width_plain_entry_points(reg21, tv, certs):
+    """All 12 keys registered, raw keys through the crate's two calls:
+    verify_strict over the 480 entries equals `strict`; verify_batch_groups
+    over the certificates (65,5xx signatures: the registry path reaches the
+    key-grouped, fused launch at 21 bits) equals the AND of `batch_rule` per
+    group with signature bits equal to `batch_rule`.  A context with no
+    registry gives the same arrays.  Each call's hits and misses add up to its
+    signatures (here: all hits)."""
+    import ntcrypto
+    rows, first, cnt, msg32, want_group, want_sig = certs
+    assert len(rows) >= 65536
+    reg21.key_cache_add(tv["keys"])
+    info = reg21.key_cache_info()
+    assert (info["keys"], info["refused"], info["pending"], info["error"], info["comb_bits"]) == (12, 0, 0, 0, 21), info
+    st, gb, sb, counts = _plain_calls(reg21, tv, certs)
+    print(counts)
+    assert np.array_equal(st, tv["strict"].astype(bool)), np.flatnonzero(st != tv["strict"].astype(bool))[:16].tolist()
+    assert np.array_equal(sb, want_sig), np.flatnonzero(sb != want_sig)[:16].tolist()
+    assert np.array_equal(gb, want_group), np.flatnonzero(gb != want_group)[:16].tolist()
+    assert [(h, m) for h, m, _ in counts] == [(n, 0) for _, _, n in counts], counts
+    plain = ntcrypto.Backend(device=0)
+    try:
+        st2, gb2, sb2, counts2 = _plain_calls(plain, tv, certs)
+    finally:
+        plain.close()
+    assert np.array_equal(st, st2) and np.array_equal(gb, gb2) and np.array_equal(sb, sb2)
+    assert all(h == 0 and m == 0 for h, m, _ in counts2)
+
+
+def test_registry_default_width_half_registered(monkeypatch, tv, certs):
+    """Only the even-numbered keys registered (four mixed-order keys, one of
+    order 8, one control) in a registry whose capacity is their number, so the
+    others can never be admitted: every call mixes the key-cache kernel at 21
+    bits with the uncached one.  Same expected arrays; hits and misses both
+    positive and adding up to the call's signatures."""
+    import ntcrypto
+    monkeypatch.delenv("NT_KEYSET_COMB_BITS", raising=False)
+    rows, first, cnt, msg32, want_group, want_sig = certs
+    even = np.arange(0, len(tv["keys"]), 2)
+    b = ntcrypto.Backend(device=0)
+    try:
+        b.set_key_cache(len(even))
+        b.key_cache_add(tv["keys"][even])
+        st, gb, sb, counts = _plain_calls(b, tv, certs)
+        b.key_cache_sync()
+        info = b.key_cache_info()
+    finally:
+        b.close()
+    print(counts, info)
+    assert (info["keys"], info["pending"], info["error"], info["comb_bits"]) == (len(even), 0, 0, 21), info
+    assert np.array_equal(st, tv["strict"].astype(bool)), np.flatnonzero(st != tv["strict"].astype(bool))[:16].tolist()
+    assert np.array_equal(sb, want_sig), np.flatnonzero(sb != want_sig)[:16].tolist()
+    assert np.array_equal(gb, want_group), np.flatnonzero(gb != want_group)[:16].tolist()
+    for h, m, n in counts:
+        assert h > 0 and m > 0 and h + m == n, counts
+    assert counts[0][0] == int(np.isin(tv["key"], even).sum())
+    assert counts[1][0] == int(np.isin(tv["key"][rows], even).sum())

@@ -213,6 +213,7 @@ def test_device_probe_exports_every_entry():
     for sym in _devprobe.EXPORTS:
         getattr(lib, sym)
     assert len(_devprobe.EXPORTS) == 28
+    lib.ntp_key_sort  # device-only: the product's counting sort (csrc/key_sort.hpp), no host twin
 
 
 def test_sha512_host_build():

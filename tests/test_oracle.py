@@ -250,6 +250,64 @@ def test_batch_groups_fixture(oracle):
         assert bool(gb[i]) == bool(np.all(sb[f:f + c]))
 
 
+def test_torsion_votes_fixture(oracle):
+    """tests/golden/torsion_votes.npz (12 keys x 40 digests under mixed-order,
+    order-8 and prime-order keys): the oracle's strict verdicts and its batch
+    rule, one signature per group, equal the fixture's two label columns on
+    every entry; every key with a torsion component has at least 8 accepted
+    entries on each branch of the reduced-scalar comb (k <= (L-1)/2 and above),
+    the bound the generator refuses to go below; k is H(R || A || M) mod L."""
+    import _torsion_votes as T
+    tv = T.load()
+    n = len(tv["key"])
+    assert n == 12 * len(tv["msg32"]) and len(tv["msg32"]) >= 40
+    assert np.array_equal(tv["pk"], tv["keys"][tv["key"]])
+    assert np.array_equal(tv["key"], np.repeat(np.arange(12), n // 12))
+    assert np.array_equal(tv["group"], np.tile(np.arange(n // 12), 12))
+    assert sorted(tv["kind"].tolist()) == [0] * 3 + [1] * 7 + [2] * 2
+    msg = tv["msg32"].reshape(-1)
+    got = oracle.verify_strict_many(tv["pk"], tv["sig"], msg, tv["off"], tv["len"], nthreads=4)
+    assert np.array_equal(got.astype(bool), tv["strict"].astype(bool))
+    gb, sb = oracle.verify_batch_groups(tv["pk"], tv["sig"], np.arange(n, dtype=np.uint64), np.ones(n, np.uint32),
+                                        tv["msg32"][tv["group"]], nthreads=4)
+    assert np.array_equal(gb.astype(bool), tv["batch_rule"].astype(bool))
+    assert np.array_equal(sb.astype(bool), tv["batch_rule"].astype(bool))
+    for ki, pk in enumerate(tv["keys"]):
+        assert oracle.point_has_torsion(pk.tobytes()) == bool(tv["kind"][ki])
+        assert oracle.point_is_small_order(pk.tobytes()) == (tv["kind"][ki] == 2)
+    for i in range(n):
+        h = hashlib.sha512(tv["sig"][i, :32].tobytes() + tv["pk"][i].tobytes() + tv["msg32"][tv["group"][i]].tobytes())
+        assert int.from_bytes(h.digest(), "little") % T.L == int.from_bytes(tv["k"][i].tobytes(), "little"), i
+    counts = T.branch_counts(tv)
+    for ki, (lo, hi) in enumerate(counts):
+        if tv["kind"][ki]:
+            assert lo >= T.MIN_PER_BRANCH and hi >= T.MIN_PER_BRANCH, (ki, counts)
+    # spoiled entries under every key, and entries the two rules label differently
+    assert all((tv["batch_rule"][tv["key"] == ki] == 0).sum() >= 2 for ki in range(12))
+    assert (tv["batch_rule"].astype(bool) & ~tv["strict"].astype(bool)).sum() >= 2 * T.MIN_PER_BRANCH
+
+
+def test_torsion_votes_arrangements():
+    """The two arrangements the GPU tests build from the fixture hold what they
+    are for: the tiled order gives every key with a torsion component waves all
+    on the high branch, waves with none on it and mixed waves; the certificates
+    have empty groups, boundaries at and across multiples of 64, an accepted
+    group ending at the last signature, accepted and rejected groups."""
+    import _torsion_votes as T
+    tv = T.load()
+    order = T.tiled_order(tv)
+    assert T.SORT_MIN <= len(order) < T.SORT_MIN + len(tv["key"])
+    waves, one_key, nw = T.wave_branches(tv, order, tv["key"][order])
+    assert one_key >= nw - 12
+    for ki, (allhi, none, mixed) in waves.items():
+        assert allhi >= 1 and none >= 1 and mixed >= 1, (ki, waves)
+    rows, first, cnt, msg32, want_group, want_sig = T.certificates(tv)
+    assert len(rows) >= T.SORT_MIN and len(msg32) == len(cnt) == len(first) == len(want_group)
+    assert np.array_equal(tv["msg32"][tv["group"][rows]], np.repeat(msg32, cnt, axis=0))
+    for f, c in zip(first[:500], cnt[:500]):
+        assert len(set(tv["key"][rows[int(f):int(f) + int(c)]].tolist())) == int(c)
+
+
 def test_torsion_points(oracle):
     meta = _json("ed25519_corpus.json")
     mine = sorted(oracle.torsion_point(i).hex() for i in range(8))
