@@ -101,7 +101,7 @@ int nt_dev_clock_probe(nt_ctx* ctx, int dev, void* stream, uint32_t iters, uint6
     NT_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dv->ordinal));
     *wall_khz = (uint64_t)khz;
   }
-  NT_TRY(nt::launch_clock_probe(iters, dv->cus, d_out2, (hipStream_t)stream));
+  NT_TRY(nt::launch_clock_probe(iters, dv->real_cus, d_out2, (hipStream_t)stream));
   return NT_OK;
 }
 

@@ -227,7 +227,8 @@ struct Device {
   std::atomic<int> ktab_ready{0};  // this slot's d_kslots / d_kpool / kcap are set
   uint32_t ws_slots = 0;
   uint32_t sign_blocks = 0;
-  uint32_t cus = 0;
+  uint32_t cus = 0;       // the CUs launches are sized for (NT_GRID_CUS; else real_cus)
+  uint32_t real_cus = 0;  // the device's
   // host entry points: chunk c's H2D copies go on cstream, cev[c] marks them
   // done, and the host launches chunk c's kernels once it has waited for cev[c]
   // (pipeline.hpp run_chunks), so copies of chunk c+1 overlap kernels of chunk c
@@ -315,11 +316,18 @@ struct Device {
     // up to 2M signatures per launch the grid is then one 512-signature block per
     // slot and the hardware dispatcher balances the tail (interleaved A/B on
     // MI355X, tools/ab_env.sh: ~1% over 1x and 2x resident).
-    uint32_t slots = (uint32_t)prop.multiProcessorCount * (uint32_t)nt::verify_occupancy() * 4;
+    // NT_GRID_CUS=<n> (read by every context and slot): launches sized as for a device of n CUs,
+    // 1 .. the real count -- the grid caps below and the `cus` the key-cache plans, their stash
+    // bound and the host chunk rounds go by.  A batch then takes the passes of the grid-stride
+    // loops that a CU partition, or a launch beyond a full device's grid, takes (tests).  The
+    // CU-mask streams above and the clock probe keep the real count.
+    real_cus = (uint32_t)prop.multiProcessorCount;
+    cus = real_cus;
+    if (const char* e = std::getenv("NT_GRID_CUS")) cus = (uint32_t)std::min<long>(std::max(1L, std::atol(e)), (long)real_cus);
+    uint32_t slots = cus * (uint32_t)nt::verify_occupancy() * 4;
     if (const char* e = std::getenv("NT_WS_SLOTS")) slots = (uint32_t)std::max(1, std::atoi(e));
     ws_slots = slots;
-    sign_blocks = (uint32_t)prop.multiProcessorCount * 8;
-    cus = (uint32_t)prop.multiProcessorCount;
+    sign_blocks = cus * 8;
     NT_TRY(hipStreamSynchronize(lane[0].stream));
     return NT_OK;
   }

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import _ingest_scenarios as S
+import _passes as P
 import _wire as W
 import ntcrypto
 from _signer_model import edge_triples, model_vote
@@ -64,10 +65,9 @@ def guards_intact(buf):
     return bool((buf[:GUARD] == 0xA5).all() and (buf[-GUARD:] == 0xA5).all())
 
 
-@pytest.mark.parametrize("n", SHAPES)
-def test_votes_shapes(signer, corpus, oracle, n):
+def check_votes(signer, corpus, n):
+    """the first n votes of the corpus into a guarded buffer, without and with digests, against the model"""
     ids, rounds, origins, wires, digests = corpus
-    assert signer.public == oracle.pubkey(SEED)
     for with_digests in (False, True):
         buf, out = guarded(n)
         got = signer.votes(ids[:n], rounds[:n], origins[:n], with_digests=with_digests, out=out)
@@ -77,6 +77,12 @@ def test_votes_shapes(signer, corpus, oracle, n):
         assert got.ctypes.data == out.ctypes.data and guards_intact(buf)
         bad = np.flatnonzero((out != wires[:n]).any(axis=1))
         assert len(bad) == 0, bad[:10]
+
+
+@pytest.mark.parametrize("n", SHAPES)
+def test_votes_shapes(signer, corpus, oracle, n):
+    assert signer.public == oracle.pubkey(SEED)
+    check_votes(signer, corpus, n)
 
 
 def test_votes_none_and_argument_rules(pair, signer, corpus):
@@ -330,3 +336,41 @@ def test_core_votes_for(oracle, monkeypatch):
             core.votes_for(rec, [sel[0], other])
     finally:
         core.close()
+
+
+# ---- later passes of the grid-stride loops: a context sized for one CU (NT_GRID_CUS=1) ----
+@pytest.fixture(scope="module")
+def one_cu():
+    """A signer in a context made under NT_GRID_CUS=1: k_signer_votes runs at most 32 rows of 64 votes and
+    k_signer_digests 8 blocks of 256 digests -- 2,048 items -- per pass.  The context's workspace proves that
+    the variable was read (tests/_passes.py)."""
+    c = P.corpus()
+    per_slot = P.slot_bytes(c)
+    with P.environment(NT_GRID_CUS=1):
+        be = ntcrypto.Backend(device=0)
+    try:
+        assert P.workspace_after_four(be, c) == P.VERIFY_OCC * 4 * per_slot
+        s = be.signer(SEED)
+        try:
+            yield s
+        finally:
+            s.close()
+    finally:
+        be.close()
+
+
+@pytest.mark.parametrize("n", [2049, 2175, NMAX])
+def test_votes_later_passes(one_cu, corpus, n):
+    """2,049: pass 2 is a row of one vote (13 16-byte stores and 1 dword); 2,175: a full row and a row of 63;
+    4,097: three passes.  Every later pass reuses the wave's LDS row."""
+    assert P.passes(n, 64, 32) == {2049: 2, 2175: 2, NMAX: 3}[n]
+    assert (n - P.SIGN_PER_CU) % 64 == {2049: 1, 2175: 63, NMAX: 1}[n] and (212 // 16, 212 % 16 // 4) == (13, 1)
+    check_votes(one_cu, corpus, n)
+
+
+@pytest.mark.parametrize("n", [2049, NMAX])
+def test_sign_digests_later_passes(one_cu, corpus, n):
+    assert P.passes(n, 256, 8) == {2049: 2, NMAX: 3}[n]
+    sig = one_cu.sign_digests(corpus[4][:n])
+    bad = np.flatnonzero((sig != corpus[3][:n, 148:]).any(axis=1))  # the model's wires carry the digests' signatures
+    assert sig.shape == (n, 64) and len(bad) == 0, bad[:10]
