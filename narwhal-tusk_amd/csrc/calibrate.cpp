@@ -66,6 +66,15 @@ int calibrate_small(nt_ctx* ctx) {
   }
   // GPU floors (the caller set small_mode = OFF: these calls run the kernels)
   {
+    // gpu_verify_us is the UNCACHED kernel's floor (small_model.hpp): the repetitions below use one
+    // key, which the key-table cache would serve from its third sighting on -- and a cached lone
+    // verify, with no square root of R and half the ladder, is no measure of a call whose keys are
+    // new.  The cache is kept out of these launches.
+    struct KtabPause {
+      nt_ctx* c;
+      explicit KtabPause(nt_ctx* x) : c(x) { for (auto& d : c->devs) d->ktab_paused.fetch_add(1); }
+      ~KtabPause() { for (auto& d : c->devs) d->ktab_paused.fetch_sub(1); }
+    } pause(ctx);
     const uint64_t off = 0, len = 0;
     uint8_t bm = 0;
     std::vector<double> t;

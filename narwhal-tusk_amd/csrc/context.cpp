@@ -178,19 +178,23 @@ static void xcache_for(Device& dv) {
 
 // The key-table cache of execution slot dv: its entry's, allocated by the entry's first verify that
 // finds NT_KTAB_KEYS non-zero -- after the comb of B and the x cache -- at that many pool entries
-// (default 2^20 = 4.16 GB) beside an index of 2^21 slots (16 MB) and the control block, both
-// zero-filled, and reserved in the entry's HBM budget.  The default halves down to 2^14 entries
+// (default 2^20 = 4.16 GB, and 1.34 GB of extension pool: the fourth tables, one unit with the
+// pool -- reserved, halved, freed and reported together) beside an index of 2^21 slots (16 MB) and
+// the control block, both zero-filled, and reserved in the entry's HBM budget.  The default halves down to 2^14 entries
 // while the budget (the cache keeps to 1/16 of a finite one: the rest is the combs') or the device
 // (the comb's rule: 4 GB stay free) does not allow it; a size asked
 // for by NT_KTAB_KEYS is tried as it is.  A cache that fits nowhere is skipped silently: the
 // kernel then runs every verification on the balanced path as before.
-// words 4..6 of the control block: the pool's address and the index mask (read by every launch)
-static hipError_t ktab_describe(void* base, void* pool) {
-  uint32_t w[3];
-  const uint64_t a = (uint64_t)(uintptr_t)pool;
+// words 4..6 and 8..9 of the control block: the pool's address, the index mask and the extension
+// pool's address (read by every launch)
+static hipError_t ktab_describe(void* base, void* pool, void* ext) {
+  uint32_t w[6] = {};
+  const uint64_t a = (uint64_t)(uintptr_t)pool, x = (uint64_t)(uintptr_t)ext;
   w[0] = (uint32_t)a;
   w[1] = (uint32_t)(a >> 32);
   w[2] = nt::kKTabIndexSlots - 1;
+  w[4] = (uint32_t)x;
+  w[5] = (uint32_t)(x >> 32);
   return hipMemcpy((uint8_t*)base + 16, w, sizeof w, hipMemcpyHostToDevice);
 }
 static void ktab_for(Device& dv) {
@@ -213,16 +217,18 @@ static void ktab_for(Device& dv) {
       if (e.budget->limit) share = e.budget->limit / 16;
     }
     for (uint64_t keys = want; keys >= 1; keys /= 2) {
-      const uint64_t bytes = index_bytes + keys * nt::ktab_entry_bytes();
+      const uint64_t bytes = index_bytes + keys * (nt::ktab_entry_bytes() + nt::ktab_ext_bytes());
       size_t fr = 0, tot = 0;
       if (hipSetDevice(e.ordinal) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) break;
       if (bytes <= share && fr >= bytes + kCombHeadroom && e.budget->reserve_aux(bytes)) {
-        void *ps = nullptr, *pp = nullptr;
+        void *ps = nullptr, *pp = nullptr, *px = nullptr;
         if (hipMalloc(&ps, index_bytes) == hipSuccess && hipMalloc(&pp, keys * nt::ktab_entry_bytes()) == hipSuccess &&
+            hipMalloc(&px, keys * nt::ktab_ext_bytes()) == hipSuccess &&
             hipMemsetAsync(ps, 0, index_bytes, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
-            ktab_describe(ps, pp) == hipSuccess) {
+            ktab_describe(ps, pp, px) == hipSuccess) {
           e.d_kslots = ps;
           e.d_kpool = pp;
+          e.d_kext = px;
           e.kcap = (uint32_t)keys;
           e.ktab_reserved = bytes;
           break;
@@ -230,6 +236,7 @@ static void ktab_for(Device& dv) {
         (void)hipGetLastError();
         if (ps) (void)hipFree(ps);
         if (pp) (void)hipFree(pp);
+        if (px) (void)hipFree(px);
         e.budget->release_aux(bytes);
       }
       if (v || keys / 2 < nt::kKTabKeysFloor) break;
@@ -238,6 +245,7 @@ static void ktab_for(Device& dv) {
   if (&dv != &e) {
     dv.d_kslots = e.d_kslots;
     dv.d_kpool = e.d_kpool;
+    dv.d_kext = e.d_kext;
     dv.kcap = e.kcap;
   }
   dv.ktab_ready.store(1, std::memory_order_release);

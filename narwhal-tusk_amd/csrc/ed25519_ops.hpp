@@ -489,6 +489,36 @@ NT_HD NT_INLINE uint32_t enc_matches(const fe& x, const uint32_t a[8], const uin
   return same & (((xw[0] & 1u) == sign) | (xz == 0));
 }
 
+// Compare of one projective R' with the encoding Rw given zi = Z^-1 (see
+// finish_compare); strict mode adds the small-order test on R'.
+template <int MODE>
+NT_HD NT_INLINE uint32_t compare_one(const ge_p2& P, const fe& zi, const uint32_t Rw[8], bool strict) {
+  fe x, y;
+  fe_mul(x, P.X, zi);
+  fe_mul(y, P.Y, zi);
+  uint32_t yw[8];
+  fe_tobytes_w(yw, y);
+  uint32_t r = enc_matches(x, yw, Rw);
+  if (strict) r &= torsion_y_words(yw) ^ 1u;  // R' on the curve: small order <=> torsion y
+  return r;
+}
+
+// The inversion of a key-cache batch (verification is public data): the
+// variable-time binary GCD (fe_inv_vt.hpp) unless -DNT_INV_VT=0 (the Fermat
+// chain, 254 squarings + 11 multiplies).
+#ifndef NT_INV_VT
+#define NT_INV_VT 1
+#endif
+NT_HD NT_INLINE void fe_invert_batch(fe& out, const fe& z) {
+#if defined(NT_EXPERIMENT_NO_INV)
+  out = z;  // timing only (wrong verdicts): what the batch inversion costs a launch
+#elif NT_INV_VT
+  fe_invert_vt(out, z);
+#else
+  fe_invert(out, z);
+#endif
+}
+
 // ---------------------------------------------------------------------------
 // The x cache: a public key's decompressed x, kept across calls in a table of
 // 32-byte slots (the verify kernel: DevXCache, kernels_common.hpp; the host
@@ -709,6 +739,28 @@ constexpr uint32_t kKtFlagShift = 28, kKtMaxEntries = 1u << kKtFlagShift;  // en
 enum : uint32_t { kKtUndecodable = 1u, kKtSmallOrder = 2u };  // header flags
 enum { kKtCntFast = 0, kKtCntBuild = 1, kKtCntOld = 2 };      // counters: wave rows
 
+// The fourth table, A''' = [2^192]A, lives outside the entry, in an extension pool
+// of kKtExtBytes per entry index (8 cached points: ten 128-B lines).  With it the
+// whole 253-bit k splits into four strings of 16 digits and the cached verify needs
+// no lattice vector and nothing of R but its bytes (verify_k4).  A policy says that
+// it can carry one with `static constexpr bool kExt = true` and then has
+//   has_ext() (wave-uniform: an extension pool is there), ext_store(idx, j, c),
+//   ext_load_signed(idx, d, c)
+// Policies without the member are three-table policies: nothing below asks them for more.
+constexpr uint32_t kKtExtBytes = kKtPerTable * kKtPointBytes;  // 1,280
+template <class KT>
+constexpr auto kt_ext_of(int) -> decltype(KT::kExt) { return KT::kExt; }
+template <class KT>
+constexpr bool kt_ext_of(long) { return false; }
+template <class KT>
+constexpr bool kKtHasExt = kt_ext_of<KT>(0);
+// an extension pool is there (wave-uniform)
+template <class KT>
+NT_HD NT_INLINE bool ktab_has_ext(const KT& kt) {
+  if constexpr (kKtHasExt<KT>) return kt.has_ext();
+  else return false;
+}
+
 struct NoKTab {
   static constexpr bool kEnabled = false;
   NT_HD NT_INLINE bool active() const { return false; }
@@ -853,18 +905,30 @@ struct KtSeenSink {
 };
 
 // ATab-shaped store adaptor of ptab_build: entries 1..8 of table t of pool entry idx
+// (t = kKtTables: the extension's table)
 template <class KT>
 struct KtStore {
   const KT& kt;
   uint32_t idx, t, on;
   NT_HD NT_INLINE void store(uint32_t entry, const ge_cached& c) {
-    if (on && entry != 0) kt.tab_store(idx, t, entry, c);
+    if (!on || entry == 0) return;
+    if constexpr (kKtHasExt<KT>) {
+      if (t >= kKtTables) {
+        kt.ext_store(idx, entry, c);
+        return;
+      }
+    }
+    kt.tab_store(idx, t, entry, c);
   }
 };
 
 // Build and publish the entries of the lanes with claim != kKtNoSlot (their keys' index slots).  Wave-uniform:
 // every lane of the row runs the arithmetic (on its own key), only the claimers
-// store.  128 doublings and three ptab_builds in a rolled loop, once per key.
+// store.  128 doublings and three ptab_builds in a rolled loop, once per key; with an
+// extension pool one round more (192 doublings, four ptab_builds), the fourth table
+// stored like the others before the drain: all of an entry's lines, then drain, release,
+// drain, then the slot word.  Without one (a null extension address, or a three-table
+// policy) exactly the three tables are built and nothing else is stored.
 // Undecodable keys get the header alone, with the flag (the full tag makes a
 // negative entry safe); small-order keys get the flag beside their tables.
 template <class KT>
@@ -880,11 +944,12 @@ NT_HD NT_INLINE void ktab_build(const uint32_t Aw[8], uint32_t claim, const KT& 
   const uint32_t ok = ge_frombytes_w(P, Aw);
   const uint32_t flags = (ok ? 0u : kKtUndecodable) | (ge_is_small_order_affine(P) ? kKtSmallOrder : 0u);
   KtStore<KT> st{kt, idx, 0, have & ok};
+  const uint32_t ntab = kKtTables + (ktab_has_ext(kt) ? 1u : 0u);
 #pragma unroll 1
-  for (uint32_t t = 0; t < kKtTables; ++t) {
+  for (uint32_t t = 0; t < ntab; ++t) {
     st.t = t;
     ptab_build(P, 0u, st, 0);
-    if (t + 1 < kKtTables) {
+    if (t + 1 < ntab) {
       ge_p2 q;
       ge_p3_to_p2(q, P);
 #pragma unroll 1
@@ -1007,6 +1072,85 @@ NT_HD NT_INLINE uint32_t verify_uv3(const uint32_t Rw[8], const uint32_t Sw[8], 
   return ok & fe_iszero(acc.X) & fe_eq(acc.Y, acc.Z);
 }
 
+// t = [k](-A) (completed) for the full k < L from the key's FOUR cached tables (pool
+// entry kidx and its extension; dead: the key has no tables, its digits are taken as
+// zero): exactly 16 windows, 60 doublings, 64 additions, nothing of R and no lattice
+// vector.  k is recoded once into 64 signed nibbles; k < L < 2^253, so the top nibble is
+// at most 1 + carry and absorbs the carry (sc_recode_w4's bound, 2^255 - 2^251, is far
+// away).  Window wi adds digit wi on A, 16 + wi on A', 32 + wi on A'', 48 + wi on A''',
+// each with its sign flipped (the tables hold +A).  The 8 digit words wait with
+// kt.dig_put / dig_get as ladder_a3r's do.  The first window seeds the accumulator from
+// its first addition and doubles nothing.
+template <class KT>
+NT_HD NT_INLINE void ladder_k4(ge_cp& t, const uint32_t k[8], uint32_t dead, const KT& kt, uint32_t kidx) {
+  {
+    uint32_t kd[8];
+    sc_recode_w4(kd, k);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) kt.dig_put((uint32_t)i, dead ? 0u : kd[i]);
+  }
+#pragma unroll 1
+  for (int wi = 15; wi >= 0; --wi) {
+    // string s has its 16 digits in words 2s, 2s + 1: the window's four, packed, so that the
+    // rolled loop below indexes nothing
+    const uint32_t dpack = ((uint32_t)kt_digit(kt, 0, wi) & 15u) | (((uint32_t)kt_digit(kt, 2, wi) & 15u) << 4) |
+                           (((uint32_t)kt_digit(kt, 4, wi) & 15u) << 8) | (((uint32_t)kt_digit(kt, 6, wi) & 15u) << 12);
+    if (wi != 15) {
+      ge_p2 acc;
+      ge_cp_to_p2(acc, t);
+#pragma unroll 1
+      for (int r = 0; r < 3; ++r) ge_dbl_p2(acc, acc);
+      ge_dbl(t, acc);
+    }
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      const int32_t d = 8 - (int32_t)(((dpack >> (4 * j)) & 15u) ^ 8u);  // the nibble, sign-extended and negated
+      ge_cached ce;
+      if (j == 3) kt.ext_load_signed(kidx, d, ce);
+      else kt.tab_load_signed(kidx, (uint32_t)j, d, ce);
+      if (wi == 15 && j == 0) {
+        // cached -> completed with T = Z (as ladder_ar's seed)
+        fe_sub4(t.X, ce.YpX, ce.YmX);
+        fe_carry(t.X);
+        fe_add(t.Y, ce.YpX, ce.YmX);
+        fe_carry(t.Y);
+        t.Z = ce.Z2;
+        t.T = ce.Z2;
+      } else {
+        ge_p3 q;
+        ge_cp_to_p3(q, t);
+        ge_add_cached(t, q, ce);
+      }
+    }
+  }
+}
+
+// The check for a key whose four tables are cached (kflags = the entry's header flags),
+// k = the full hash scalar:
+//   ok  <=>  s < L, A decodes, (strict) A is not of small order, and R' = [s]B - [k]A
+//            encodes to R's bytes the way dalek compares points (enc_matches), (strict)
+//            R' not of small order
+// -- verify_uv's verdict for every input: with v odd and below L, [v]([s]B - [k]A - R) is
+// the identity only if R decodes to R' itself.  R is never decompressed, the lane's table
+// workspace is not touched, and s goes to the comb as it is.
+template <int MODE, class WComb, class KT>
+NT_HD NT_INLINE uint32_t verify_k4(const uint32_t Rw[8], const uint32_t Sw[8], const uint32_t k[8], uint32_t kflags,
+                                   const WComb& wb, const KT& kt, uint32_t kidx) {
+  const uint32_t dead = (kflags & kKtUndecodable) ? 1u : 0u;
+  uint32_t ok = sc_is_canonical(Sw) & (dead ^ 1u);
+  if (MODE == kStrict) ok &= (kflags & kKtSmallOrder) ? 0u : 1u;
+  ge_cp t;
+  ladder_k4(t, k, dead, kt, kidx);
+  ge_p3 acc;
+  ge_cp_to_p3(acc, t);
+  wcomb_acc(acc, Sw, wb);
+  fe zi;
+  fe_invert_batch(zi, acc.Z);
+  ge_p2 P;
+  ge_p3_to_p2(P, acc);
+  return ok & compare_one<MODE>(P, zi, Rw, MODE == kStrict);
+}
+
 // One verification (A, R, s encodings as words), half-size scalars:
 //   ok  <=>  s < L, A and R decode, (strict) neither is small order, and
 //            [v s mod L]B - [u]A - [v]R == identity     (= [v]([s]B - [k]A - R))
@@ -1030,7 +1174,8 @@ NT_HD NT_INLINE uint32_t verify_one_kt(const uint32_t Aw[8], const uint32_t Rw[8
     KtProbe kp;
     ktab_probe(kp, Aw, kt);
     const uint32_t kidx = ktab_ready_index(kp, kt);
-    if (!wave_any(kidx == kKtNoSlot)) {
+    // a policy that can carry the fourth table takes the fast path only with one
+    if ((!kKtHasExt<KT> || ktab_has_ext(kt)) && !wave_any(kidx == kKtNoSlot)) {
       kt.acquire();  // ONE acquire between the slot loads and the first pool load
       uint32_t tag[8], kflags, same = 1;
       kt.hdr_load(kidx, tag, kflags);
@@ -1046,10 +1191,14 @@ NT_HD NT_INLINE uint32_t verify_one_kt(const uint32_t Aw[8], const uint32_t Rw[8
   hram_scalar(k, Rw, Aw, msg, len);
   uint32_t u[8], v[8], uneg;
   if (KT::kEnabled && fast) {
-    int ub, vb;
-    sc_unbalanced(u, uneg, v, k, ub, vb);
-    return verify_uv3<MODE>(Rw, Sw, u, uneg, v, ub, vb, kent >> kKtFlagShift, at, wb, kt,
-                            kent & ((1u << kKtFlagShift) - 1u));
+    if constexpr (kKtHasExt<KT>) {
+      return verify_k4<MODE>(Rw, Sw, k, kent >> kKtFlagShift, wb, kt, kent & ((1u << kKtFlagShift) - 1u));
+    } else {
+      int ub, vb;
+      sc_unbalanced(u, uneg, v, k, ub, vb);
+      return verify_uv3<MODE>(Rw, Sw, u, uneg, v, ub, vb, kent >> kKtFlagShift, at, wb, kt,
+                              kent & ((1u << kKtFlagShift) - 1u));
+    }
   }
   const int bits = sc_halfsize(u, uneg, v, k);
   return verify_uv<MODE>(Aw, Rw, Sw, u, uneg, v, bits, at, wb, xc, KtSeenSink<KT>{kt});
@@ -1154,36 +1303,6 @@ NT_HD NT_INLINE uint32_t cached_point(ge_p3& acc, uint32_t meta, const uint32_t 
 #endif
   wcomb_acc(acc, Sw, cb);
   return okj;
-}
-
-// Compare of one projective R' with the encoding Rw given zi = Z^-1 (see
-// finish_compare); strict mode adds the small-order test on R'.
-template <int MODE>
-NT_HD NT_INLINE uint32_t compare_one(const ge_p2& P, const fe& zi, const uint32_t Rw[8], bool strict) {
-  fe x, y;
-  fe_mul(x, P.X, zi);
-  fe_mul(y, P.Y, zi);
-  uint32_t yw[8];
-  fe_tobytes_w(yw, y);
-  uint32_t r = enc_matches(x, yw, Rw);
-  if (strict) r &= torsion_y_words(yw) ^ 1u;  // R' on the curve: small order <=> torsion y
-  return r;
-}
-
-// The inversion of a key-cache batch (verification is public data): the
-// variable-time binary GCD (fe_inv_vt.hpp) unless -DNT_INV_VT=0 (the Fermat
-// chain, 254 squarings + 11 multiplies).
-#ifndef NT_INV_VT
-#define NT_INV_VT 1
-#endif
-NT_HD NT_INLINE void fe_invert_batch(fe& out, const fe& z) {
-#if defined(NT_EXPERIMENT_NO_INV)
-  out = z;  // timing only (wrong verdicts): what the batch inversion costs a launch
-#elif NT_INV_VT
-  fe_invert_vt(out, z);
-#else
-  fe_invert(out, z);
-#endif
 }
 
 // N cached verifications per lane with ONE inversion (Montgomery's trick).

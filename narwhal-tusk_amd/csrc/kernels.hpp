@@ -37,18 +37,20 @@ inline uint32_t xcache_slots_pow2(unsigned long long want, uint32_t cap) {
 // The key-table cache of a verify launch (kernels_common.hpp DevKTab; ed25519_ops.hpp KTab):
 // base = the control block (kKTabCtlBytes: words 0..3 = entries handed out, fast-path rows, builds,
 // old-path rows; words 4..5 = the pool's device address, 128-byte aligned entries of
-// ktab_entry_bytes(); word 6 = index slots - 1, a power of two of whole buckets) followed by the
-// index slots of 8 bytes; cap = the pool entries this launch may use.  base == nullptr = none.
+// ktab_entry_bytes(); word 6 = index slots - 1, a power of two of whole buckets; words 8..9 = the
+// extension pool's device address, ktab_ext_bytes() per entry index: the fourth table) followed by
+// the index slots of 8 bytes; cap = the pool entries this launch may use.  base == nullptr = none.
 struct KTabArgs {
   void* base = nullptr;
   uint32_t cap = 0;
 };
 constexpr uint32_t kKTabCtlBytes = 128;
-constexpr uint32_t kKTabKeysDefault = 1u << 20;   // 4.16 GB of entries
+constexpr uint32_t kKTabKeysDefault = 1u << 20;   // 4.16 GB of entries + 1.34 GB of extension
 constexpr uint32_t kKTabKeysFloor = 1u << 14;     // the default halves down to this, then none
 constexpr uint32_t kKTabIndexSlots = 1u << 21;    // 16 MB
 constexpr uint32_t kKTabCtlWords = 4;
 size_t ktab_entry_bytes();
+size_t ktab_ext_bytes();
 hipError_t launch_verify(int mode, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
                          uint64_t msg_bytes, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
                          const uint32_t* d_combB, int bbits, void* d_ws, uint32_t ws_slots, uint64_t* d_out_words,

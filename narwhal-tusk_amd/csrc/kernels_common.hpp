@@ -235,15 +235,20 @@ struct DevXCache {
 // aligned multiples of 128 bytes, so no cache line a reader may hold goes stale.
 // Indices: slots are masked here, entry indices are checked against cap by the callers
 // (ktab_ready_index, ktab_build) before they get here, table and point numbers are clamped here.
+// -DNT_KTAB4=0 (A/B builds): a three-table policy -- cached rows run verify_uv3 as before the
+// fourth table, and nothing reads the extension pool.
+#ifndef NT_KTAB4
+#define NT_KTAB4 1
+#endif
 struct DevKTab {
   static constexpr bool kEnabled = true;
   static constexpr uint32_t kEntryQuads = kKtEntryBytes / 16, kHeaderQuads = kKtHeaderBytes / 16;
   static_assert(kKtEntryBytes % 128 == 0 && kKtPointBytes == 160, "entry = whole 128-byte lines of 10-quad points");
   // One pointer and the launch's capacity are all a launch carries in registers.  base: the
   // control block (128 bytes: words 0..3 = entries handed out and the three row counters,
-  // words 4..5 = the pool's address, word 6 = slots - 1; the last three written once, before the
-  // first launch, and read here through the scalar path: they are never handed off), then the
-  // index slots.
+  // words 4..5 = the pool's address, word 6 = slots - 1, words 8..9 = the extension pool's
+  // address; these five written once, before the first launch, and read here through the scalar
+  // path: they are never handed off), then the index slots.
   uint32_t* base;
   uint32_t cap;
   NT_D NT_INLINE bool active() const { return base != nullptr; }
@@ -315,21 +320,43 @@ struct DevKTab {
     e[1] = make_uint4(tag[4], tag[5], tag[6], tag[7]);
     e[2] = make_uint4(flags, 0u, 0u, 0u);
   }
-  NT_D NT_INLINE void tab_store(uint32_t idx, uint32_t t, uint32_t j, const ge_cached& c) const {
+  // The extension pool: cap x kKtExtBytes, the fourth table ([2^192]A) of the entry with the
+  // same index.  Its address is words 8..9 of the control block, written once beside words 4..6
+  // and read the same way; zero = no fourth table (the callers ask has_ext() first: a null
+  // extension is never dereferenced).
+  static constexpr bool kExt = NT_KTAB4 != 0;
+  static constexpr uint32_t kExtQuads = kKtExtBytes / 16;
+  static_assert(kKtExtBytes % 128 == 0, "extension entry = whole 128-byte lines");
+  NT_D NT_INLINE uint4* ext_ptr() const { return (uint4*)(*(const unsigned long long*)(base + 8)); }
+  NT_D NT_INLINE bool has_ext() const { return ext_ptr() != nullptr; }
+  NT_D NT_INLINE uint4* ext_point(uint32_t idx, uint32_t j) const {
+    return ext_ptr() + (size_t)idx * kExtQuads + ((j - 1u) & (kKtPerTable - 1u)) * 10u;
+  }
+  NT_D NT_INLINE void point_store(uint4* p, const ge_cached& c) const {
     uint32_t w[40];
 #pragma unroll
     for (int i = 0; i < 10; ++i) {
       w[i] = c.YpX.v[i]; w[10 + i] = c.YmX.v[i]; w[20 + i] = c.Z2.v[i]; w[30 + i] = c.T2d.v[i];
     }
-    uint4* p = point(idx, t, j);
 #pragma unroll
     for (int q = 0; q < 10; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
   }
+  NT_D NT_INLINE void tab_store(uint32_t idx, uint32_t t, uint32_t j, const ge_cached& c) const {
+    point_store(point(idx, t, j), c);
+  }
+  NT_D NT_INLINE void ext_store(uint32_t idx, uint32_t j, const ge_cached& c) const { point_store(ext_point(idx, j), c); }
   // point |d| of table t with the sign of d; d = 0: the identity, synthesized (the load still
   // goes to a valid point of the entry and is dropped)
   NT_D NT_INLINE void tab_load_signed(uint32_t idx, uint32_t t, int32_t d, ge_cached& c) const {
     const uint32_t a = (uint32_t)(d < 0 ? -d : d);
-    const uint4* p = point(idx, t, a);
+    point_load_signed(point(idx, t, a), a, d < 0, c);
+  }
+  // the same of the fourth table
+  NT_D NT_INLINE void ext_load_signed(uint32_t idx, int32_t d, ge_cached& c) const {
+    const uint32_t a = (uint32_t)(d < 0 ? -d : d);
+    point_load_signed(ext_point(idx, a), a, d < 0, c);
+  }
+  NT_D NT_INLINE void point_load_signed(const uint4* p, uint32_t a, bool neg, ge_cached& c) const {
     uint32_t w[40];
 #pragma unroll
     for (int q = 0; q < 10; ++q) {
@@ -345,7 +372,7 @@ struct DevKTab {
       c.Z2.v[i] = a ? w[20 + i] : z.Z2.v[i];
       c.T2d.v[i] = a ? w[30 + i] : z.T2d.v[i];
     }
-    ge_cached_cneg(c, d < 0);
+    ge_cached_cneg(c, neg);
   }
 };
 

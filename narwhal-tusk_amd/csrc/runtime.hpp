@@ -221,10 +221,12 @@ struct Device {
   // names its entry) -- and never rewrites or frees an entry before the context closes.
   void* d_kslots = nullptr;     // the control block, then nt::kKTabIndexSlots slots of 8 bytes (nt::KTabArgs::base)
   void* d_kpool = nullptr;      // kcap entries of nt::ktab_entry_bytes()
+  void* d_kext = nullptr;       // kcap fourth tables of nt::ktab_ext_bytes(): allocated, shared and freed with the pool
   uint32_t kcap = 0;
   uint64_t ktab_reserved = 0;   // (entry) its bytes in the budget
   bool ktab_tried = false;      // (entry) under tables_mu
   std::atomic<int> ktab_ready{0};  // this slot's d_kslots / d_kpool / kcap are set
+  std::atomic<int> ktab_paused{0};  // (entry) > 0: launches carry no cache (calibrate_small's uncached floor)
   uint32_t ws_slots = 0;
   uint32_t sign_blocks = 0;
   uint32_t cus = 0;       // the CUs launches are sized for (NT_GRID_CUS; else real_cus)
@@ -269,6 +271,7 @@ struct Device {
     if (entry == this && d_xtab) (void)hipFree(d_xtab);
     if (entry == this && d_kslots) (void)hipFree(d_kslots);
     if (entry == this && d_kpool) (void)hipFree(d_kpool);
+    if (entry == this && d_kext) (void)hipFree(d_kext);
     for (hipEvent_t e : {lane[0].ws_done, lane[0].stash_done, lane[1].ws_done, lane[1].stash_done})
       if (e) (void)hipEventDestroy(e);
     for (auto& e : cev)
@@ -379,7 +382,7 @@ struct Device {
   // first entries (entries beyond it are misses, none is added), a larger one changes nothing.
   nt::KTabArgs ktab() const {
     nt::KTabArgs kt;
-    if (!d_kslots || !d_kpool) return kt;
+    if (!d_kslots || !d_kpool || !d_kext || entry->ktab_paused.load(std::memory_order_relaxed)) return kt;
     uint32_t cap = kcap;
     if (const char* e = std::getenv("NT_KTAB_KEYS")) cap = (uint32_t)std::min<unsigned long long>(std::strtoull(e, nullptr, 10), kcap);
     if (cap) {
