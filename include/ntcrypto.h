@@ -495,13 +495,14 @@ void nt_host_free(void *p);
  * only when it is proven to be the key's x -- and rates do: a batch whose keys
  * this context has verified before runs about 6 % faster.
  *
- * The same kernel keeps, for a key it meets a second time, the window tables of
- * A, [2^64]A, [2^128]A and [2^192]A in a pool per device entry (NT_KTAB_KEYS
- * entries of 3,968 bytes plus 1,280 bytes of extension each, default 2^20 =
- * 5.5 GB, halved down to 2^14 while the HBM budget or the device does not allow
- * it; 0 = off; read again at every launch) and verifies later signatures of that
- * key with a ladder of under half the doublings, comparing [s]B - [k]A with R's
- * bytes instead of decompressing R.  Entries are
+ * The same kernel keeps, for a key it meets a second time, a comb of A (33 affine
+ * multiples of A: 4 teeth 64 bits apart, 4 blocks of 16 columns) in a pool per
+ * device entry (NT_KTAB_KEYS keys of 8,192 bytes each -- a 3,968-byte entry and a
+ * 4,224-byte comb -- default 2^20 = 8.6 GB beside a 16 MB index, halved down to
+ * 2^14 while the HBM budget or the device does not allow it; 0 = off; read again
+ * at every launch) and verifies later signatures of that key with a ladder of 15
+ * doublings, comparing [s]B - [k]A with R's bytes instead of decompressing R.
+ * Entries are
  * only added, never replaced, until the context closes.  Verdicts do not depend
  * on the pool.  nt_memory_info(ctx, dev | NT_INFO_KTAB, out8), after the launches
  * of interest have completed: out8[0] entries in use, out8[1] capacity, out8[2] device bytes,

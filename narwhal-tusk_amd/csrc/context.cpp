@@ -178,14 +178,15 @@ static void xcache_for(Device& dv) {
 
 // The key-table cache of execution slot dv: its entry's, allocated by the entry's first verify that
 // finds NT_KTAB_KEYS non-zero -- after the comb of B and the x cache -- at that many pool entries
-// (default 2^20 = 4.16 GB, and 1.34 GB of extension pool: the fourth tables, one unit with the
-// pool -- reserved, halved, freed and reported together) beside an index of 2^21 slots (16 MB) and
+// (default 2^20 = 4.16 GB, and 4.43 GB of second pool: the keys' combs, 4,224 B each -- 8,192 B per
+// key, 8.6 GB in all; a -DNT_KCOMB=0 build keeps fourth tables there, 1,280 B each -- one unit with
+// the pool: reserved, halved, freed and reported together) beside an index of 2^21 slots (16 MB) and
 // the control block, both zero-filled, and reserved in the entry's HBM budget.  The default halves down to 2^14 entries
 // while the budget (the cache keeps to 1/16 of a finite one: the rest is the combs') or the device
 // (the comb's rule: 4 GB stay free) does not allow it; a size asked
 // for by NT_KTAB_KEYS is tried as it is.  A cache that fits nowhere is skipped silently: the
 // kernel then runs every verification on the balanced path as before.
-// words 4..6 and 8..9 of the control block: the pool's address, the index mask and the extension
+// words 4..6 and 8..9 of the control block: the pool's address, the index mask and the second
 // pool's address (read by every launch)
 static hipError_t ktab_describe(void* base, void* pool, void* ext) {
   uint32_t w[6] = {};

@@ -383,7 +383,8 @@ static int keyset_occ() {
 }
 int verify_occupancy() { return verify_occ(); }
 size_t ktab_entry_bytes() { return kKtEntryBytes; }
-size_t ktab_ext_bytes() { return kKtExtBytes; }
+// per entry index of the second pool: the key's comb, or (-DNT_KCOMB=0) its fourth table
+size_t ktab_ext_bytes() { return DevKTab::kComb ? kKtCombBytes : kKtExtBytes; }
 int keyset_occupancy() { return keyset_occ(); }
 
 hipError_t launch_verify(int mode, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,

@@ -38,14 +38,15 @@ inline uint32_t xcache_slots_pow2(unsigned long long want, uint32_t cap) {
 // base = the control block (kKTabCtlBytes: words 0..3 = entries handed out, fast-path rows, builds,
 // old-path rows; words 4..5 = the pool's device address, 128-byte aligned entries of
 // ktab_entry_bytes(); word 6 = index slots - 1, a power of two of whole buckets; words 8..9 = the
-// extension pool's device address, ktab_ext_bytes() per entry index: the fourth table) followed by
+// second pool's device address, ktab_ext_bytes() per entry index: the key's comb, or the fourth
+// table of a -DNT_KCOMB=0 build) followed by
 // the index slots of 8 bytes; cap = the pool entries this launch may use.  base == nullptr = none.
 struct KTabArgs {
   void* base = nullptr;
   uint32_t cap = 0;
 };
 constexpr uint32_t kKTabCtlBytes = 128;
-constexpr uint32_t kKTabKeysDefault = 1u << 20;   // 4.16 GB of entries + 1.34 GB of extension
+constexpr uint32_t kKTabKeysDefault = 1u << 20;   // 4.16 GB of entries + 4.43 GB of combs (8,192 B per key)
 constexpr uint32_t kKTabKeysFloor = 1u << 14;     // the default halves down to this, then none
 constexpr uint32_t kKTabIndexSlots = 1u << 21;    // 16 MB
 constexpr uint32_t kKTabCtlWords = 4;

@@ -118,6 +118,7 @@ struct WideComb {
 struct WsATab {
   uint4* ws;
   uint32_t slot;
+  static constexpr uint32_t kEntries = kAEntries;  // what ktab_build_comb checks its 16 bases against
 #if NT_ATAB_LANE_MAJOR
   static constexpr size_t kQuadStride = 1;
   NT_D NT_INLINE uint4* at(uint32_t entry) const {
@@ -237,8 +238,14 @@ struct DevXCache {
 // (ktab_ready_index, ktab_build) before they get here, table and point numbers are clamped here.
 // -DNT_KTAB4=0 (A/B builds): a three-table policy -- cached rows run verify_uv3 as before the
 // fourth table, and nothing reads the extension pool.
+// -DNT_KCOMB=0 (A/B builds): the second pool holds the fourth table and cached rows run verify_k4,
+// kernel and allocation as before the comb; the default fills it with the keys' combs (verify_kc).
+// NT_KTAB4=0 implies no comb.
 #ifndef NT_KTAB4
 #define NT_KTAB4 1
+#endif
+#ifndef NT_KCOMB
+#define NT_KCOMB 1
 #endif
 struct DevKTab {
   static constexpr bool kEnabled = true;
@@ -324,11 +331,43 @@ struct DevKTab {
   // same index.  Its address is words 8..9 of the control block, written once beside words 4..6
   // and read the same way; zero = no fourth table (the callers ask has_ext() first: a null
   // extension is never dereferenced).
+  // What the second pool holds is a compile-time choice: the key's comb (kComb, the default:
+  // cap x kKtCombBytes, 33 lines of 128 B per entry index -- the window tables are then never
+  // built for a key that gets an entry through verify_n, and has_ext() is false for good) or
+  // the fourth table (-DNT_KCOMB=0).
   static constexpr bool kExt = NT_KTAB4 != 0;
-  static constexpr uint32_t kExtQuads = kKtExtBytes / 16;
-  static_assert(kKtExtBytes % 128 == 0, "extension entry = whole 128-byte lines");
+  static constexpr bool kComb = NT_KTAB4 != 0 && NT_KCOMB != 0;
+  static constexpr uint32_t kExtQuads = kKtExtBytes / 16, kCombQuads = kKtCombBytes / 16, kLineQuads = kKcLineBytes / 16;
+  static_assert(kKtExtBytes % 128 == 0 && kKtCombBytes % 128 == 0, "second-pool entry = whole 128-byte lines");
   NT_D NT_INLINE uint4* ext_ptr() const { return (uint4*)(*(const unsigned long long*)(base + 8)); }
-  NT_D NT_INLINE bool has_ext() const { return ext_ptr() != nullptr; }
+  NT_D NT_INLINE bool has_ext() const { return !kComb && ext_ptr() != nullptr; }
+  NT_D NT_INLINE bool has_comb() const { return kComb && ext_ptr() != nullptr; }
+  // comb line `entry` (clamped) of entry index idx: 7 quads and a half, bytes 120..127 are never written
+  NT_D NT_INLINE uint4* comb_line(uint32_t idx, uint32_t entry) const {
+    return ext_ptr() + (size_t)idx * kCombQuads + (entry < kKcEntries ? entry : kKcEntries - 1u) * kLineQuads;
+  }
+  NT_D NT_INLINE void comb_store(uint32_t idx, uint32_t entry, const ge_niels& q) const {
+    uint32_t w[30];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) { w[i] = q.ypx.v[i]; w[10 + i] = q.ymx.v[i]; w[20 + i] = q.xy2d.v[i]; }
+    uint4* p = comb_line(idx, entry);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) p[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    *(uint2*)(p + 7) = make_uint2(w[28], w[29]);
+  }
+  NT_D NT_INLINE void comb_load(uint32_t idx, uint32_t entry, ge_niels& q) const {
+    uint32_t w[30];
+    const uint4* p = comb_line(idx, entry);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      const uint4 v = p[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    const uint2 h = *(const uint2*)(p + 7);
+    w[28] = h.x; w[29] = h.y;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) { q.ypx.v[i] = w[i]; q.ymx.v[i] = w[10 + i]; q.xy2d.v[i] = w[20 + i]; }
+  }
   NT_D NT_INLINE uint4* ext_point(uint32_t idx, uint32_t j) const {
     return ext_ptr() + (size_t)idx * kExtQuads + ((j - 1u) & (kKtPerTable - 1u)) * 10u;
   }

@@ -221,7 +221,7 @@ struct Device {
   // names its entry) -- and never rewrites or frees an entry before the context closes.
   void* d_kslots = nullptr;     // the control block, then nt::kKTabIndexSlots slots of 8 bytes (nt::KTabArgs::base)
   void* d_kpool = nullptr;      // kcap entries of nt::ktab_entry_bytes()
-  void* d_kext = nullptr;       // kcap fourth tables of nt::ktab_ext_bytes(): allocated, shared and freed with the pool
+  void* d_kext = nullptr;       // the second pool, kcap combs of nt::ktab_ext_bytes(): allocated, shared and freed with the pool
   uint32_t kcap = 0;
   uint64_t ktab_reserved = 0;   // (entry) its bytes in the budget
   bool ktab_tried = false;      // (entry) under tables_mu
