@@ -90,7 +90,8 @@ def _p(a):
 ENTRIES = ["fe_mul", "fe_sq", "fe_sq_wide", "fe_carry", "fe_tobytes", "fe_frombytes", "fe_invert", "sc_reduce512",
            "sc_muladd", "sc_mul", "sc_reduce_half", "sc_recode_w4", "sc_is_canonical", "sc_halfsize", "hram",
            "point_checks", "ladder_uv", "sc_unbalanced", "ktab_fill", "ktab_point", "ladder_uv3", "wcomb_build",
-           "wcomb_free", "wcomb_entries", "wcomb_guard", "wcomb_digits", "wcomb_acc", "key_comb_sum"]
+           "wcomb_free", "wcomb_entries", "wcomb_guard", "wcomb_digits", "wcomb_acc", "key_comb_sum",
+           "kcomb_fill", "kcomb_line", "kc_picks", "ladder_kc", "compare_one", "verify_kc"]
 
 # the probe's key table (tests/cpp/nt_probe_items.hpp, laid out as kernels_common.hpp DevKTab reads it):
 # a 128-byte control block (word 0: entries handed out), KT_SLOTS index slots of 8 bytes
@@ -107,12 +108,30 @@ def ktab_blob(capacity):
     return np.zeros(KT_POOL_OFF + capacity * KT_ENTRY_BYTES, np.uint8)
 
 
+# the comb items' table (nt_probe_items.hpp kcomb_probe_bytes): the layout above, then `capacity` combs of
+# KC_COMB_BYTES (33 lines of KC_LINE_BYTES: 30 limbs, 8 bytes never written) and KC_GUARD_BYTES that
+# nothing may write.  Pool, combs and guard start as KC_FILL, so that every byte a build stores shows.
+KC_COMB_BYTES, KC_LINE_BYTES, KC_LINES, KC_SIGNED, KC_GUARD_BYTES, KC_FILL = 4224, 128, 33, 32, 8192, 0xA5
+
+
+def kcomb_comb_off(capacity):
+    return KT_POOL_OFF + capacity * KT_ENTRY_BYTES
+
+
+def kcomb_blob(capacity):
+    """an empty key table of `capacity` entries with a comb pool and the guard behind it"""
+    blob = np.full(kcomb_comb_off(capacity) + capacity * KC_COMB_BYTES + KC_GUARD_BYTES, KC_FILL, np.uint8)
+    blob[:KT_POOL_OFF] = 0
+    return blob
+
+
 class Runner:
     """Bulk calls into a library of `<prefix><entry>(n, ...)` functions; a nonzero
     return (a hipError_t on the device) raises."""
 
     def __init__(self, lib, prefix, name):
         self.lib, self.prefix, self.name = lib, prefix, name
+        self.waves = prefix == "ntp_"  # 64 consecutive items run in lockstep (the host: one after the other)
 
     def _call(self, entry, n, *args):
         fn = getattr(self.lib, self.prefix + entry)
@@ -273,6 +292,62 @@ class Runner:
                    _p(out))
         raw = out.tobytes()
         return [raw[i:i + 32] for i in range(0, len(raw), 32)]
+
+    # the key-table cache's comb path, over a kcomb_blob(capacity)
+    def kcomb_fill(self, keys, blob, capacity):
+        """builds the comb of each key (probe, take, the four-argument ktab_build) in `blob`; the index slot
+        each item won, or KT_NO_SLOT"""
+        a = np.frombuffer(b"".join(keys), np.uint32).copy()
+        slot = np.zeros(len(keys), np.uint32)
+        self._call("kcomb_fill", len(keys), _p(a), _p(blob), ctypes.c_uint32(capacity), _p(slot))
+        return [int(x) for x in slot]
+
+    def kcomb_line(self, keys, lines, blob, capacity):
+        """(entry index or KT_NO_SLOT, tag match, header flags, the 30 limbs comb_load hands out for line
+        `line` of the key's comb) per (key, line)"""
+        a = np.frombuffer(b"".join(keys), np.uint32).copy()
+        ln = np.array(lines, np.uint32)
+        out3, limbs = np.zeros((len(keys), 3), np.uint32), np.zeros((len(keys), 30), np.uint32)
+        self._call("kcomb_line", len(keys), _p(a), _p(ln), _p(blob), ctypes.c_uint32(capacity), _p(out3), _p(limbs))
+        return [(int(o[0]), int(o[1]), int(o[2]), q) for o, q in zip(out3, limbs)]
+
+    def kc_picks(self, ks):
+        """per scalar: (the 64 lookups (block, index within the block, negate) in ladder_kc's order, c)"""
+        a = _words(ks)
+        out = np.zeros((len(a), 65), np.uint32)
+        self._call("kc_picks", len(a), _p(a), _p(out))
+        return [([((int(w) & 0xff) // 8, (int(w) & 0xff) % 8, int(w) >> 8) for w in row[:64]], int(row[64])) for row in out]
+
+    def ladder_kc(self, kidx, ks, dead, blob, capacity):
+        """encoding of ladder_kc's [k](-A) over the comb of pool entry kidx per item (dead: the identity)"""
+        ki, dd = np.array(kidx, np.uint32), np.array(dead, np.uint32)
+        k = _words(ks)
+        out = np.zeros((len(k), 8), np.uint32)
+        self._call("ladder_kc", len(k), _p(ki), _p(k), _p(dd), _p(blob), ctypes.c_uint32(capacity), _p(out))
+        raw = out.tobytes()
+        return [raw[i:i + 32] for i in range(0, len(raw), 32)]
+
+    def compare_one(self, items):
+        """compare_one's bit per item (x, y, z, R encoding, mode): R' = (x z : y z : z) against R's bytes;
+        mode 0 strict, 1 cofactorless"""
+        x, y, z = (_words([it[j] % P for it in items]) for j in range(3))
+        r = np.frombuffer(b"".join(it[3] for it in items), np.uint32).copy()
+        mode = np.array([it[4] for it in items], np.uint32)
+        out = np.zeros(len(items), np.uint32)
+        self._call("compare_one", len(items), _p(x), _p(y), _p(z), _p(r), _p(mode), _p(out))
+        return [int(b) for b in out]
+
+    def verify_kc(self, items, blob, capacity):
+        """verify_kc's bit per item (entry index, header flags, R encoding, s, k, mode) over the combs in
+        `blob` and the live comb set's comb of B (16 bits)"""
+        ki, kf = (np.array([it[j] for it in items], np.uint32) for j in (0, 1))
+        r = np.frombuffer(b"".join(it[2] for it in items), np.uint32).copy()
+        s, k = _words([it[3] for it in items]), _words([it[4] for it in items])
+        mode = np.array([it[5] for it in items], np.uint32)
+        out = np.zeros(len(items), np.uint32)
+        self._call("verify_kc", len(items), _p(ki), _p(kf), _p(r), _p(s), _p(k), _p(mode), _p(blob),
+                   ctypes.c_uint32(capacity), _p(out))
+        return [int(b) for b in out]
 
     # the wide combs: one comb set is live per library, between wcomb_build and wcomb_free
     def _raw(self, entry, *args):
@@ -1451,4 +1526,475 @@ def check_wcomb_refusals(run):
         finally:
             run.wcomb_free()
     refuses(run.wcomb_guard)                                       # freed: no live set
+    return refused
+
+
+# --------------------------------------------------------------------------
+# the key-table cache's comb path: ktab_build_comb, kc_recode / kc_pick, ladder_kc, compare_one,
+# verify_kc (ed25519_ops.hpp), over the runner's comb table
+# --------------------------------------------------------------------------
+KC_CAPACITY = 80
+KC_EDGES = (0, 1, 2, 3, L - 1, L - 2, 1 << 252, (1 << 253) - 1, (1 << 253) - 2)
+# the block boundaries 2^(16 j) -1, +0, +1; j = 4, 8, 12 are the tooth boundaries
+KC_BOUNDS = tuple((1 << (16 * j)) + d for j in range(1, 16) for d in (-1, 0, 1))
+
+
+class Mul:
+    """[k]Q for many k and one Q of the point model: the powers [2^i]Q once, then additions"""
+
+    def __init__(self, Q):
+        self.M, self.pw = model(), [Q]
+        for _ in range(255):
+            self.pw.append(self.M.padd(self.pw[-1], self.pw[-1]))
+
+    def __call__(self, k):
+        acc, i = self.M.IDENT, 0
+        while k:
+            if k & 1:
+                acc = self.M.padd(acc, self.pw[i])
+            k >>= 1
+            i += 1
+        return acc
+
+
+def entry_scalar(block, index):
+    """the integer multiple of A that comb line 8 block + index holds (ed25519_ops.hpp, "The comb")"""
+    r = [1 if index >> t & 1 else -1 for t in range(3)]
+    return (1 << 16 * block) * ((1 << 192) + r[2] * (1 << 128) + r[1] * (1 << 64) + r[0])
+
+
+@functools.lru_cache(maxsize=None)
+def kcomb_fill_order():
+    """ktab_keys() in the order one fill call takes them, three waves:
+    wave 0 -- the duplicated random key on all 64 lanes (64 racing for one slot: exactly one claimer);
+    wave 1 -- 64 distinct keys met nowhere else (every lane a claimer), the 8 undecodable ones among them;
+    wave 2 -- the 8 keys left and 5 duplicates of two of them: a ragged wave of 13 lanes."""
+    keys, kinds = ktab_keys()
+    kind_of = dict(zip(keys, kinds))
+    k0 = keys[0]
+    assert keys[:5] == (k0,) * 5
+    others = [k for k in dict.fromkeys(keys) if k != k0]
+    undec = [k for k in others if kind_of[k] == "undecodable"]
+    rest = [k for k in others if kind_of[k] != "undecodable"]
+    assert len(undec) == 8 and len(rest) == 64
+    wave1 = rest[4:60] + undec
+    left = rest[:4] + rest[60:]
+    wave2 = left + [left[0]] * 3 + [left[5]] * 2
+    order = [k0] * 64 + wave1 + wave2
+    assert len(wave1) == 64 and len(set(wave1)) == 64 and set(order) == set(keys) and len(order) % 64 == 13
+    return tuple(order)
+
+
+@functools.lru_cache(maxsize=None)
+def kcomb_expected():
+    """per distinct key: None (undecodable) or (is_small, the 33 affine niels triples of its comb lines)"""
+    M = model()
+    want = {}
+    for e in dict.fromkeys(ktab_keys()[0]):
+        A = M.decode(e)
+        if A is None:
+            want[e] = None
+            continue
+        mul = Mul(A)
+        pts = [mul(entry_scalar(n // 8, n % 8)) for n in range(KC_SIGNED)] + [A]
+        want[e] = (M.is_small(A), tuple(_niels(p) for p in pts))
+    return want
+
+
+def _comb_lines(blob, capacity):
+    """the comb pool of a blob as (capacity, 33, 128) bytes"""
+    off = kcomb_comb_off(capacity)
+    return blob[off:off + capacity * KC_COMB_BYTES].reshape(capacity, KC_LINES, KC_LINE_BYTES)
+
+
+def _pool_entries(blob, capacity):
+    return blob[KT_POOL_OFF:KT_POOL_OFF + capacity * KT_ENTRY_BYTES].reshape(capacity, KT_ENTRY_BYTES)
+
+
+def kcomb_filled(run):
+    """the runner's comb table of ktab_keys(), filled once by one kcomb_fill call in kcomb_fill_order():
+    (blob, slots won, entry index per key).  Kept on the runner: the ladder and the verdicts read it."""
+    if not hasattr(run, "_kcomb"):
+        order = kcomb_fill_order()
+        blob = kcomb_blob(KC_CAPACITY)
+        slots = run.kcomb_fill(order, blob, KC_CAPACITY)
+        distinct = list(dict.fromkeys(order))
+        seen = run.kcomb_line(distinct, [KC_SIGNED] * len(distinct), blob, KC_CAPACITY)  # a second launch
+        run._kcomb = (blob, slots, {k: s[0] for k, s in zip(distinct, seen)})
+    return run._kcomb
+
+
+def check_kcomb_tables(run):
+    """ktab_probe / ktab_take / ktab_build with a comb pool (ktab_build_comb: the 16 bases parked in the
+    lane's table workspace, 12 additions per block, one inversion for 32 lines read back from the
+    pool) over the runner's table, in the waves of kcomb_fill_order().  One entry per distinct key
+    with the model's tag and flags; lines 0..31 through comb_load, reduced mod p, are the affine
+    niels form of entry_scalar(block, index) A and line 32 is A, a line number past 32 is line 32;
+    the pool's own bytes say the same, bytes 120..127 of every line keep the prefill, of the entry
+    pool only headers are written, an undecodable key gets a header alone, nothing past the last
+    entry or in the guard is touched.  Then a pool of 4 filled by one wave of 64 claimers (4 win,
+    60 find the pool exhausted, undecodable keys among them) and a second call that finds it full.
+    Returns the number of lines compared."""
+    order, want = kcomb_fill_order(), kcomb_expected()
+    distinct = list(want)
+    blob, slots, idx_of = kcomb_filled(run)
+    cap = KC_CAPACITY
+    assert int(blob[:4].view(np.uint32)[0]) == len(distinct), (run.name, "pool used")
+    assert not blob[16:28].any() and not blob[32:40].any(), (run.name, "addresses handed back")
+    won = [s != KT_NO_SLOT for s in slots]
+    assert sum(won[:64]) == 1, (run.name, "wave 0: one claimer", sum(won[:64]))
+    assert all(won[64:128]), (run.name, "wave 1: 64 claimers")
+    for k in distinct:  # one CAS winner per key, and its slot names the entry
+        mine = [s for kk, s in zip(order, slots) if kk == k and s != KT_NO_SLOT]
+        assert len(mine) == 1 and mine[0] < KT_SLOTS, (run.name, k.hex(), mine)
+        assert _slot_state(blob, mine[0]) == KT_READY0 + idx_of[k], (run.name, k.hex())
+    assert sorted(idx_of[k] for k in distinct) == list(range(len(distinct))), (run.name, "entry indices")
+    lines, entries = _comb_lines(blob, cap), _pool_entries(blob, cap)
+    numbers = list(range(KC_LINES)) + [KC_LINES, 40, 0xffffffff]   # the last three: comb_line's clamp
+    items = [(k, n) for k in distinct for n in numbers]
+    got = run.kcomb_line([k for k, _ in items], [n for _, n in items], blob, cap)
+    n_small = n_dead = n_lines = 0
+    for (k, n), (idx, same, flags, limbs) in zip(items, got):
+        assert idx == idx_of[k] and same == 1, (run.name, k.hex(), n, idx, same)
+        line = min(n, KC_SIGNED)
+        raw = lines[idx, line]
+        assert limbs.tobytes() == raw[:120].tobytes(), (run.name, k.hex(), "line", n, "comb_load != the pool's bytes")
+        assert (raw[120:] == KC_FILL).all(), (run.name, k.hex(), "line", n, "bytes 120..127")
+        if want[k] is None:
+            assert flags == KT_UNDECODABLE, (run.name, k.hex(), flags)
+            assert (raw == KC_FILL).all(), (run.name, k.hex(), "line", n, "an undecodable key has no lines")
+            n_dead += 1
+            continue
+        small, niels = want[k]
+        assert flags == (KT_SMALL_ORDER if small else 0), (run.name, k.hex(), flags)
+        n_small += small
+        g = tuple(value(limbs[10 * c:10 * c + 10]) % P for c in range(3))
+        assert g == niels[line], (run.name, k.hex(), "line", n)
+        assert is_reduced(limbs[:10]) and is_reduced(limbs[10:20]) and is_reduced(limbs[20:]), (run.name, k.hex(), n)
+        n_lines += 1
+    assert n_small >= 8 * len(numbers) and n_dead == 8 * len(numbers)
+    for k in distinct:  # the entry pool: the tag and the flags, and nothing behind the header
+        e = entries[idx_of[k]]
+        assert e[:32].tobytes() == k, (run.name, k.hex(), "tag")
+        assert (e[KT_HEADER_BYTES:] == KC_FILL).all(), (run.name, k.hex(), "bytes behind the header")
+    used = len(distinct)
+    assert (entries[used:] == KC_FILL).all() and (lines[used:] == KC_FILL).all(), (run.name, "past the last entry")
+    assert (blob[-KC_GUARD_BYTES:] == KC_FILL).all(), (run.name, "guard")
+    # a pool of 4 entries in a fresh table: one wave of 64 distinct claimers, then everything else
+    cap = 4
+    blob4 = kcomb_blob(cap)
+    wave = list(order[64:128])
+    slots4 = run.kcomb_fill(wave, blob4, cap)
+    # in lockstep all 64 lanes find the pool empty, claim a slot and ask the pool: 4 win, 60 find it
+    # exhausted; one after the other, the fifth key on finds the pool full and claims nothing
+    claimers = sum(s != KT_NO_SLOT for s in slots4)
+    assert claimers == (64 if run.waves else cap), (run.name, "claimers", claimers)
+    assert int(blob4[:4].view(np.uint32)[0]) == claimers, (run.name, "every claimer asked the pool")
+    later = run.kcomb_fill([k for k in order if k not in wave], blob4, cap)
+    assert all(s == KT_NO_SLOT for s in later), (run.name, "a full pool is left alone")
+    assert int(blob4[:4].view(np.uint32)[0]) == claimers
+    seen = run.kcomb_line(distinct, [KC_SIGNED] * len(distinct), blob4, cap)
+    ready = {k: s for k, s in zip(distinct, seen) if s[0] != KT_NO_SLOT}
+    assert sorted(s[0] for s in ready.values()) == list(range(cap)) and set(ready) <= set(wave), (run.name, sorted(ready))
+    lines4, entries4 = _comb_lines(blob4, cap), _pool_entries(blob4, cap)
+    for k, (idx, same, flags, limbs) in ready.items():
+        assert same == 1 and entries4[idx, :32].tobytes() == k, (run.name, k.hex())
+        assert (entries4[idx, KT_HEADER_BYTES:] == KC_FILL).all(), (run.name, k.hex())
+        if want[k] is None:
+            assert flags == KT_UNDECODABLE and (lines4[idx] == KC_FILL).all(), (run.name, k.hex())
+            continue
+        for n in range(KC_LINES):
+            w = lines4[idx, n, :120].view(np.uint32)
+            assert tuple(value(w[10 * c:10 * c + 10]) % P for c in range(3)) == want[k][1][n], (run.name, k.hex(), n)
+            assert (lines4[idx, n, 120:] == KC_FILL).all(), (run.name, k.hex(), n)
+        n_lines += KC_LINES
+    for k, s in zip(wave, slots4):  # the claimers that found the pool exhausted: seen for good
+        if k not in ready and s != KT_NO_SLOT:
+            assert _slot_state(blob4, s) == KT_SEEN, (run.name, k.hex(), _slot_state(blob4, s))
+    states = blob4[KT_CTL_BYTES:KT_POOL_OFF].view(np.uint64) >> np.uint64(32)
+    assert sorted(int(s) for s in states[states >= KT_READY0]) == [KT_READY0 + i for i in range(cap)], run.name
+    assert not np.any(states == KT_CLAIMED), (run.name, "a slot left claimed")
+    # every byte behind the four combs -- here: the guard -- and behind the four entries is untouched
+    assert blob4[kcomb_comb_off(cap) + cap * KC_COMB_BYTES:].size == KC_GUARD_BYTES
+    assert (blob4[kcomb_comb_off(cap) + cap * KC_COMB_BYTES:] == KC_FILL).all(), (run.name, "guard of the pool of 4")
+    return n_lines
+
+
+@functools.lru_cache(maxsize=None)
+def kc_pick_scalars():
+    rng = random.Random(20261021)
+    return KC_EDGES + KC_BOUNDS + tuple(rng.randrange(L) for _ in range(330))
+
+
+def check_kc_picks(run):
+    """kc_recode + the 64 kc_pick lookups in ladder_kc's order (on the device through the LDS digit
+    cells): block i mod 4, index below 8, and summed the way the ladder sums them -- one doubling
+    before every column but the first; a negated entry counts positive, because the ladder sums
+    -[K]A over tables of +A -- exactly k + c = k | 1 with c = 1 - (k & 1), for the edge scalars,
+    the tooth and block boundaries and seeded random k.  Returns the number of pick vectors."""
+    ks = kc_pick_scalars()
+    assert {k & 1 for k in ks[:9]} == {0, 1} and all(k < 1 << 253 for k in ks)
+    for k, (picks, c) in zip(ks, run.kc_picks(ks)):
+        acc = 0
+        for i, (block, index, neg) in enumerate(picks):
+            assert block == i % 4 and 0 <= index < 8 and neg in (0, 1), (run.name, hex(k), i, block, index, neg)
+            if i % 4 == 0 and i:
+                acc *= 2
+            acc += (1 if neg else -1) * entry_scalar(block, index)
+        assert c == 1 - (k & 1) and acc == k + c == k | 1, (run.name, hex(k), c)
+    return len(ks)
+
+
+def _keys_of_kind(kind, n):
+    keys, kinds = ktab_keys()
+    return [k for k, x in dict(zip(keys, kinds)).items() if x == kind][:n]
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_kc_cases():
+    """(key encodings, scalars, dead flags, expected encodings) of five waves and a tail of 21 lanes.
+    Waves 0..2 carry the 9 edge and 45 boundary scalars and 10 random ones, lane l of wave r on key
+    (l + r) mod 8 of {3 honest, 2 mixed-order, 2 small-order, 1 undecodable}: both parities, eight
+    entries and -- the undecodable key's lanes, as verify_kc runs them -- dead lanes beside live
+    ones in every wave, and every scalar live on at least two keys.  Wave 3: one k on every lane;
+    wave 4: 64 distinct random k; the tail: random."""
+    M = model()
+    keyset = _keys_of_kind("random", 3) + _keys_of_kind("mixed", 2) + _keys_of_kind("torsion", 8)[3:5] + \
+        _keys_of_kind("undecodable", 1)
+    assert len(keyset) == 8 and M.is_small(M.decode(keyset[5])) and not M.is_ident(M.decode(keyset[5]))
+    rng = random.Random(4242)
+    base = list(KC_EDGES + KC_BOUNDS) + [rng.randrange(L) for _ in range(10)]
+    assert len(base) == 64
+    same = rng.randrange(L)
+    As, ks = [], []
+    for r in range(3):
+        for lane in range(64):
+            As.append(keyset[(lane + r) % 8])
+            ks.append(base[lane])
+    for lane in range(64):
+        As.append(keyset[lane % 8])
+        ks.append(same)
+    for lane in range(64 + 21):
+        As.append(keyset[(3 * lane + 1) % 8])
+        ks.append(rng.randrange(L))
+    assert len(set(ks[256:320])) == 64
+    dead = [1 if M.decode(A) is None else 0 for A in As]
+    for w in range(5):
+        sl = slice(64 * w, 64 * w + 64)
+        assert 0 < sum(dead[sl]) < 64 and len(set(As[sl])) == 8, w
+        assert w == 3 or {k & 1 for k, d in zip(ks[sl], dead[sl]) if not d} == {0, 1}, w
+    for lane in range(64):  # every edge and boundary scalar: live on two keys at least
+        assert sum(1 - dead[64 * r + lane] for r in range(3)) >= 2
+    mul = {A: Mul(M.pneg(M.decode(A))) for A in keyset if M.decode(A) is not None}
+    want = [M.encode(M.IDENT if d else mul[A](k)) for A, k, d in zip(As, ks, dead)]
+    return tuple(As), tuple(ks), tuple(dead), tuple(want)
+
+
+def check_ladder_kc(run):
+    """ladder_kc's result is [k](-A) by the model, as an integer multiple, for honest, mixed-order
+    and small-order keys over the combs the runner built (see ladder_kc_cases): lanes of one wave
+    differ in parity -- kc_load's `off` of the correction --, in entry, and in dead or live.
+    Returns the number of results compared."""
+    As, ks, dead, want = ladder_kc_cases()
+    blob, _, idx_of = kcomb_filled(run)
+    got = run.ladder_kc([idx_of[A] for A in As], ks, dead, blob, KC_CAPACITY)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (run.name, "wave", i // 64, "lane", i % 64, "k", hex(ks[i]), "key", As[i].hex(), "dead", dead[i])
+    return len(ks)
+
+
+def _affine(p):
+    zi = model().inv(p[2])
+    return p[0] * zi % P, p[1] * zi % P
+
+
+@functools.lru_cache(maxsize=None)
+def compare_one_cases():
+    """(x, y, z, R encoding, mode, expected bit): the cases of tests/test_ktab4_host.py's
+    test_compare_at_function_level, z random (never 1) unless said"""
+    M = model()
+    rng = random.Random(7)
+    z = lambda: rng.randrange(2, P)
+    cases = []
+    for i in range(20):
+        Rp = M.pmul(rng.randrange(1, L), M.BASE)
+        x, y = _affine(Rp)
+        enc = M.encode(Rp)
+        other = bytes(enc[:31]) + bytes([enc[31] ^ 0x80])
+        wrong = (int.from_bytes(enc, "little") ^ 2).to_bytes(32, "little")
+        for mode in (0, 1):
+            zz = 1 if i == 0 else z()
+            cases += [(x, y, zz, enc, mode, 1),       # R's own encoding
+                      (x, y, zz, other, mode, 0),     # enc(-R'): same y, the other sign
+                      (x, y, zz, wrong, mode, 0)]
+    # x' = 0: (0, 1) and (0, -1); a set sign bit ("negative zero") passes the cofactorless rule; both
+    # points are of small order: strict rejects
+    for y in (1, P - 1):
+        for sign in (0, 1):
+            R = (y | sign << 255).to_bytes(32, "little")
+            cases += [(0, y, z(), R, 1, 1), (0, y, z(), R, 0, 0)]
+    # y_R = y' + p fits in 255 bits only for y' < 19: the curve points with such y
+    seen = 0
+    for y in range(19):
+        pt = M.decode(y.to_bytes(32, "little"))
+        if pt is None:
+            continue
+        x, _ = _affine(pt)
+        R = ((y + P) | (x & 1) << 255).to_bytes(32, "little")
+        flip = ((y + P) | ((x & 1) ^ 1) << 255).to_bytes(32, "little")
+        cases += [(x, y, z(), R, 1, 1), (x, y, z(), R, 0, 0 if M.is_small(pt) else 1),
+                  (x, y, z(), flip, 1, 1 if x == 0 else 0)]
+        seen += 1
+    assert seen >= 2
+    for t in M.TORSION:  # every point of small order: rejected in strict, accepted in cofactorless
+        x, y = _affine(t)
+        cases += [(x, y, z(), M.encode(t), 0, 0), (x, y, z(), M.encode(t), 1, 1)]
+    return tuple(cases)
+
+
+def check_compare_one(run):
+    """compare_one with a chosen R' = (x z : y z : z), z inverted by fe_invert_batch, in both modes:
+    R's own encoding, the other sign, one bit of y off, x = 0 under a set sign bit, y >= p
+    encodings, R' of small order under strict, z = 1 and z != 1.  Returns the number of bits."""
+    cases = compare_one_cases()
+    got = run.compare_one([c[:5] for c in cases])
+    for i, (c, g) in enumerate(zip(cases, got)):
+        assert g == c[5], (run.name, "item", i, "mode", c[4], "x", hex(c[0]), "y", hex(c[1]), "R", c[3].hex(), g)
+    return len(cases)
+
+
+def model_verify_kc(A_enc, kflags, R, s, k, mode):
+    """verify_kc's verdict from the point model: s < L, the key decodes (its header says so),
+    (strict) the key is not of small order, R' = [s]B - [k]A equals the point R's bytes decode to
+    -- y taken mod p, the sign bit ignored where x = 0, as dalek compares --, (strict) R' is not
+    of small order"""
+    M = model()
+    if s >= L or kflags & KT_UNDECODABLE or (mode == 0 and kflags & KT_SMALL_ORDER):
+        return 0
+    Rp = M.padd(M.pmul(s, M.BASE), M.pmul(k, M.pneg(M.decode(A_enc))))
+    Rd = M.decode(R)
+    ok = Rd is not None and M.peq(Rd, Rp)
+    if mode == 0:
+        ok = ok and not M.is_small(Rp)
+    return int(ok)
+
+
+@functools.lru_cache(maxsize=None)
+def verify_kc_cases():
+    """(key encoding, header flags -- None: the entry's own --, R, s, k, what) per case; each runs in
+    both modes, and all of them share one wave"""
+    M = model()
+    keys, kinds = ktab_keys()
+    rng = random.Random(55)  # ktab_keys' own generator: the seeds a of its random keys A = [a]B
+    seeds = [rng.randrange(1, M.L) for _ in range(24)]
+    a, A = seeds[1], keys[5]
+    assert M.encode(M.pmul(a, M.BASE)) == A and kinds[5] == "random"
+    rng = random.Random(56)
+    ident = M.encode(M.IDENT)
+    flip = lambda e, bit: (int.from_bytes(e, "little") ^ (1 << bit)).to_bytes(32, "little")
+    cases = [(A, None, ident, 0, 0, "s = 0, k = 0: R' is the identity")]
+    for k in (1, 2, L - 1, rng.randrange(L)):
+        cases.append((A, None, ident, k * a % L, k, "s = k a: R' is the identity, k != 0"))
+    for k in (rng.randrange(L), rng.randrange(L) | 1, rng.randrange(L) & ~1, 0, L - 1):
+        r = rng.randrange(1, L)
+        R, s = M.encode(M.pmul(r, M.BASE)), (r + k * a) % L
+        cases.append((A, None, R, s, k, "honest"))
+        if len(cases) < 12:
+            cases.append((A, None, R, s + L, k, "s + L"))
+            cases.append((A, None, flip(R, 3), s, k, "a bit of R's y flipped"))
+            cases.append((A, None, flip(R, 255), s, k, "R's sign bit flipped"))
+            cases.append((A, KT_UNDECODABLE, R, s, k, "honest, header says undecodable"))
+            cases.append((A, KT_SMALL_ORDER, R, s, k, "honest, header says small order"))
+    undec = _keys_of_kind("undecodable", 1)[0]
+    cases.append((undec, None, ident, 0, 0, "an undecodable key's own entry"))
+    T = _keys_of_kind("torsion", 8)[3]
+    for k in (rng.randrange(L), 5):
+        r = rng.randrange(1, L)
+        R = M.encode(M.padd(M.pmul(r, M.BASE), M.pmul(k, M.pneg(M.decode(T)))))
+        cases.append((T, None, R, r, k, "a small-order key, R exact"))
+    cases.append((T, 0, R, r, k, "a small-order key whose header does not say so"))
+    mixed = _keys_of_kind("mixed", 1)[0]
+    k, r = rng.randrange(L), rng.randrange(1, L)
+    R = M.encode(M.padd(M.pmul(r, M.BASE), M.pmul(k, M.pneg(M.decode(mixed)))))
+    cases.append((mixed, None, R, r, k, "a mixed-order key, R exact"))
+    cases.append((mixed, None, R, (r + 1) % L, k, "a mixed-order key, s off by one"))
+    assert 2 * len(cases) <= 64, len(cases)
+    return tuple(cases)
+
+
+def check_verify_kc(run):
+    """verify_kc's bit for chosen (R, s, k) that no hash reaches, over the runner's combs and the
+    16-bit comb of B the probe builds, both modes of every case in ONE wave.  Expected bits:
+    model_verify_kc.  The corpus rule each case restates (tests/golden):
+      s = 0, k = 0 and s = k a, R = the identity's encoding -- small_order_R / all_zero_sig: the
+        cofactorless rule accepts the exact equation, strict rejects a small-order R;
+      honest -- honest; s + L -- s_plus_L (s >= L: rejected in both modes);
+      a bit of R flipped -- wrong_msg_bitflip / R_not_on_curve (the equation fails, or R decodes to nothing);
+      header undecodable -- A_not_on_curve (rejected in both modes);
+      header small order, and a small-order key with R exact -- small_order_A / small_A_R_exact
+        (strict rejects, the cofactorless rule accepts);
+      a mixed-order key with R exact -- mixed_A_valid (accepted in both modes: the check is the
+        cofactorless single-signature equation, nothing is multiplied by 8).
+    Returns the number of verdicts compared."""
+    M = model()
+    cases = verify_kc_cases()
+    blob, _, idx_of = kcomb_filled(run)
+    items, want = [], []
+    for A, kflags, R, s, k, _ in cases:
+        own = (KT_UNDECODABLE if M.decode(A) is None else (KT_SMALL_ORDER if M.is_small(M.decode(A)) else 0))
+        f = own if kflags is None else kflags
+        for mode in (0, 1):
+            items.append((idx_of[A], f, R, s, k, mode))
+            want.append(0 if M.decode(A) is None else model_verify_kc(A, f, R, s, k, mode))
+    assert len(items) <= 64 and 8 <= sum(want) <= len(want) - 8
+    try:
+        run.wcomb_build(16, (M.encode(M.BASE),), 0, 1)
+        got = run.verify_kc(items, blob, KC_CAPACITY)
+    finally:
+        run.wcomb_free()
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (run.name, "lane", i, cases[i // 2][5], "mode", items[i][5], "got", g, "want", w)
+    return len(items)
+
+
+def check_kcomb_refusals(run):
+    """The comb entry points refuse, before anything runs: a capacity of 0, an entry index at the
+    capacity, a scalar k >= 2^253, a mode other than 0 or 1, a dead flag or header flags out of
+    range, and verify_kc without a 16-bit comb of B.  Returns the number of refused calls."""
+    M = model()
+    blob, _, idx_of = kcomb_filled(run)
+    cap = KC_CAPACITY
+    ident, key = M.encode(M.IDENT), ktab_keys()[0][0]
+    refused = 0
+
+    def refuses(call, *args):
+        nonlocal refused
+        try:
+            call(*args)
+        except RuntimeError:
+            refused += 1
+            return
+        raise AssertionError((run.name, "not refused", call.__name__))
+
+    refuses(run.kcomb_fill, [key], blob, 0)
+    refuses(run.kcomb_line, [key], [0], blob, 0)
+    refuses(run.kc_picks, [1, 1 << 253])
+    refuses(run.ladder_kc, [0, cap], [1, 1], [0, 0], blob, cap)
+    refuses(run.ladder_kc, [0, 0], [1, 1 << 253], [0, 0], blob, cap)
+    refuses(run.ladder_kc, [0, 0], [1, 1], [0, 2], blob, cap)
+    refuses(run.compare_one, [(0, 1, 1, ident, 0), (0, 1, 1, ident, 2)])
+    good = (0, 0, ident, 0, 0, 1)
+    refuses(run.verify_kc, [good], blob, cap)                      # no live comb of B
+    try:
+        run.wcomb_build(16, (M.encode(M.BASE),), 0, 1)
+        assert run.verify_kc([good], blob, cap) == [1]
+        for bad in ((cap, 0, ident, 0, 0, 1), (0, 4, ident, 0, 0, 1), (0, 0, ident, 0, 1 << 253, 1), (0, 0, ident, 0, 0, 2)):
+            refuses(run.verify_kc, [good, bad], blob, cap)
+    finally:
+        run.wcomb_free()
+    try:
+        run.wcomb_build(18, (M.encode(M.BASE),), 0, 1)
+        refuses(run.verify_kc, [good], blob, cap)                  # not the narrowest width
+    finally:
+        run.wcomb_free()
     return refused

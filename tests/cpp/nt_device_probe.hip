@@ -14,6 +14,13 @@
 // schedule), k_wcomb_entries (WideComb::load / load_corr), k_wcomb_acc, k_key_comb_sum --
 // the last three over combs that ntp_wcomb_build makes with the product's own
 // k_wcomb_bases / k_wcomb_fill through wcomb_build<W> (csrc/wcomb_build.hpp).
+// The comb path of the key-table cache runs over a second blob (nt_probe_items.hpp
+// kcomb_probe_bytes: the key table, then a comb pool whose address words 8..9 of the control block
+// carry, then a guard), so DevKTab::has_comb() holds as in the product: k_kcomb_fill (probe, take,
+// ktab_build_comb with the lane's WsATab), k_kcomb_line (DevKTab::comb_load and comb_line's clamp),
+// k_kc_picks (kc_recode / kc_pick through the LDS digit cells), k_ladder_kc, k_compare_one and
+// k_verify_kc, the last with the narrowest comb of B that ntp_wcomb_build makes.  The three-table
+// kernels keep their blob, in which words 8..9 stay zero.
 // ntp_key_sort runs the product's counting sort (csrc/key_sort.hpp launch_key_sort: k_key_hist,
 // k_key_scatter) and hands back the permutation a key-cache launch would walk.
 // Never linked into libntcrypto.so.
@@ -177,22 +184,80 @@ __global__ void __launch_bounds__(kBlock)
 // The probe's key table on the device: `blob` (ktab_probe_bytes(cap) bytes, owned by the
 // caller) copied in, words 4..6 of the control block -- the pool's address and slots - 1 --
 // written from the host before the launch, and copied back after it with those three zeroed.
+// comb: the blob of the comb items (kcomb_probe_bytes(cap) bytes), words 8..9 carrying the
+// address of the comb pool behind the entries, zeroed again on the way back.
 struct DevBlob {
   Dev d;
   uint8_t* host;
   size_t bytes;
-  DevBlob(hipError_t* e, uint8_t* blob, uint32_t cap) : d(e, blob, ntp::ktab_probe_bytes(cap)), host(blob),
-                                                        bytes(ntp::ktab_probe_bytes(cap)) {
+  bool comb;
+  DevBlob(hipError_t* e, uint8_t* blob, uint32_t cap, bool with_comb = false)
+      : d(e, blob, with_comb ? ntp::kcomb_probe_bytes(cap) : ntp::ktab_probe_bytes(cap)), host(blob),
+        bytes(with_comb ? ntp::kcomb_probe_bytes(cap) : ntp::ktab_probe_bytes(cap)), comb(with_comb) {
     if (*e != hipSuccess) return;
     const unsigned long long pool = (unsigned long long)(uintptr_t)((uint8_t*)d.p + ntp::kKtProbePoolOff);
     const uint32_t w[3] = {(uint32_t)pool, (uint32_t)(pool >> 32), ntp::kKtProbeSlots - 1u};
     *e = hipMemcpy((uint8_t*)d.p + 16, w, sizeof w, hipMemcpyHostToDevice);
+    if (*e != hipSuccess || !comb) return;
+    const unsigned long long cp = (unsigned long long)(uintptr_t)((uint8_t*)d.p + ntp::kcomb_probe_comb_off(cap));
+    const uint32_t c[2] = {(uint32_t)cp, (uint32_t)(cp >> 32)};
+    *e = hipMemcpy((uint8_t*)d.p + 32, c, sizeof c, hipMemcpyHostToDevice);
   }
   void back() const {
     d.back(host, bytes);
-    if (*d.err == hipSuccess) std::memset(host + 16, 0, 12);
+    if (*d.err != hipSuccess) return;
+    std::memset(host + 16, 0, 12);
+    if (comb) std::memset(host + 32, 0, 8);
   }
 };
+
+// The comb kernels of the key-table cache: DevKTab over the comb blob (kComb is true under the
+// product's default flags, so has_comb() holds and ktab_build takes ktab_build_comb), the
+// lane's WsATab as the verify kernel hands it over.  The build is wave-uniform: lanes past n
+// run it on the last key with no claim.
+static_assert(DevKTab::kComb, "the probe is built with the product's defaults: the second pool holds combs");
+__global__ void __launch_bounds__(kBlock)
+    k_kcomb_fill(uint64_t n, const uint32_t* A, uint32_t* base, uint32_t cap, uint4* ws, uint32_t* slot) {
+  const uint64_t i = item_index();
+  WsATab at{ws, blockIdx.x};
+  const DevKTab kt{base, cap};
+  ntp::item_kcomb_fill(i < n ? i : n - 1, A, kt, at, slot, i < n);
+}
+__global__ void __launch_bounds__(kBlock) k_kcomb_line(uint64_t n, const uint32_t* A, const uint32_t* line, uint32_t* base,
+                                                       uint32_t cap, uint32_t* out3, uint32_t* limbs) {
+  const uint64_t i = item_index();
+  const DevKTab kt{base, cap};
+  if (i < n) ntp::item_kcomb_line(i, A, line, kt, out3, limbs);
+}
+// only the LDS digit cells of the policy are used: no table behind it
+__global__ void __launch_bounds__(kBlock) k_kc_picks(uint64_t n, const uint32_t* k, uint32_t* o) {
+  const uint64_t i = item_index();
+  const DevKTab kt{nullptr, 0};
+  if (i < n) ntp::item_kc_picks(i, k, kt, o);
+}
+// lanes past n run the last item again and write nothing
+__global__ void __launch_bounds__(kBlock) k_ladder_kc(uint64_t n, const uint32_t* kidx, const uint32_t* k,
+                                                      const uint32_t* dead, uint32_t* base, uint32_t cap, uint32_t* o) {
+  const uint64_t i = item_index();
+  const DevKTab kt{base, cap};
+  ntp::item_ladder_kc(i < n ? i : n - 1, kidx, k, dead, kt, o, i < n);
+}
+// lanes past n leave at once (fe_invert_vt's wave-level exit sees the lanes the caller filled)
+__global__ void __launch_bounds__(kBlock) k_compare_one(uint64_t n, const uint32_t* x, const uint32_t* y, const uint32_t* z,
+                                                        const uint32_t* R, const uint32_t* mode, uint32_t* o) {
+  const uint64_t i = item_index();
+  if (i < n) ntp::item_compare_one(i, x, y, z, R, mode, o);
+}
+// comb: the comb of B (key 0 of the live comb set); lanes past n run the last item again and write nothing
+template <int W>
+__global__ void __launch_bounds__(kBlock)
+    k_verify_kc(uint64_t n, const uint32_t* comb, const uint32_t* kidx, const uint32_t* kflags, const uint32_t* R,
+                const uint32_t* S, const uint32_t* k, const uint32_t* mode, uint32_t* base, uint32_t cap, uint32_t* o) {
+  const uint64_t i = item_index();
+  const DevKTab kt{base, cap};
+  const WideComb<W> wb{comb};
+  ntp::item_verify_kc(i < n ? i : n - 1, kidx, kflags, R, S, k, mode, wb, kt, o, i < n);
+}
 
 // The wide-comb kernels: the product's WideComb<W> over the probe's comb set (key[i] picks
 // the comb of item i).  Lanes past n leave at once: key_comb_sum's wave_any then sees
@@ -569,6 +634,85 @@ int ntp_key_comb_sum(uint64_t n, const uint32_t* key, const uint32_t* meta, cons
                ds.as<uint32_t>(), dout.as<uint32_t>())
   });
   dout.back(out_enc8, 32 * n);
+  return (int)err;
+}
+
+// ---- the key-table cache's comb path.  blob: ntp::kcomb_probe_bytes(capacity) bytes -- control
+// block, index, pool entries, comb pool, guard -- prefilled by the caller; entry indices, scalars
+// (k < 2^253) and modes are checked here, on the host, before anything is launched.
+int ntp_kcomb_fill(uint64_t n, const uint32_t* A8, uint8_t* blob, uint32_t capacity, uint32_t* slot) {
+  if (!ntp::kcomb_cap_ok(capacity)) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  const size_t ws_bytes = (size_t)grid(n) * kBlock * kAEntries * kAQuads * sizeof(uint4);
+  Dev dA(&err, A8, 32 * n), ds(&err, nullptr, 4 * n), dws(&err, nullptr, ws_bytes);
+  DevBlob db(&err, blob, capacity, true);
+  NTP_LAUNCH(k_kcomb_fill, dA.as<uint32_t>(), db.d.as<uint32_t>(), capacity, dws.as<uint4>(), ds.as<uint32_t>())
+  ds.back(slot, 4 * n);
+  db.back();
+  return (int)err;
+}
+// line[i]: any number (comb_line clamps it to the last line)
+int ntp_kcomb_line(uint64_t n, const uint32_t* A8, const uint32_t* line, uint8_t* blob, uint32_t capacity, uint32_t* out3,
+                   uint32_t* limbs30) {
+  if (!ntp::kcomb_cap_ok(capacity)) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dA(&err, A8, 32 * n), dl(&err, line, 4 * n), do3(&err, nullptr, 12 * n), dq(&err, nullptr, 120 * n);
+  DevBlob db(&err, blob, capacity, true);
+  NTP_LAUNCH(k_kcomb_line, dA.as<uint32_t>(), dl.as<uint32_t>(), db.d.as<uint32_t>(), capacity, do3.as<uint32_t>(),
+             dq.as<uint32_t>())
+  do3.back(out3, 12 * n);
+  dq.back(limbs30, 120 * n);
+  db.back();
+  return (int)err;
+}
+int ntp_kc_picks(uint64_t n, const uint32_t* k8, uint32_t* out65) {
+  if (!ntp::kc_scalars_ok(n, k8)) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dk(&err, k8, 32 * n), dout(&err, nullptr, 4 * ntp::kKcPickWords * n);
+  NTP_LAUNCH(k_kc_picks, dk.as<uint32_t>(), dout.as<uint32_t>())
+  dout.back(out65, 4 * ntp::kKcPickWords * n);
+  return (int)err;
+}
+int ntp_ladder_kc(uint64_t n, const uint32_t* kidx, const uint32_t* k8, const uint32_t* dead, uint8_t* blob,
+                  uint32_t capacity, uint32_t* out8) {
+  if (!ntp::kcomb_cap_ok(capacity) || !ntp::ladder_kc_args_ok(n, kidx, k8, dead, capacity)) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev di(&err, kidx, 4 * n), dk(&err, k8, 32 * n), dd(&err, dead, 4 * n), dout(&err, nullptr, 32 * n);
+  DevBlob db(&err, blob, capacity, true);
+  NTP_LAUNCH(k_ladder_kc, di.as<uint32_t>(), dk.as<uint32_t>(), dd.as<uint32_t>(), db.d.as<uint32_t>(), capacity,
+             dout.as<uint32_t>())
+  dout.back(out8, 32 * n);
+  db.back();
+  return (int)err;
+}
+int ntp_compare_one(uint64_t n, const uint32_t* x8, const uint32_t* y8, const uint32_t* z8, const uint32_t* R8,
+                    const uint32_t* mode, uint32_t* out1) {
+  if (!ntp::modes_ok(n, mode)) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev dx(&err, x8, 32 * n), dy(&err, y8, 32 * n), dz(&err, z8, 32 * n), dR(&err, R8, 32 * n), dm(&err, mode, 4 * n),
+      dout(&err, nullptr, 4 * n);
+  NTP_LAUNCH(k_compare_one, dx.as<uint32_t>(), dy.as<uint32_t>(), dz.as<uint32_t>(), dR.as<uint32_t>(), dm.as<uint32_t>(),
+             dout.as<uint32_t>())
+  dout.back(out1, 4 * n);
+  return (int)err;
+}
+// the comb of B: key 0 of the live comb set, which must be the narrowest width (ntp_wcomb_build
+// of B alone, not negated); any 256-bit s stays inside that table
+int ntp_verify_kc(uint64_t n, const uint32_t* kidx, const uint32_t* kflags, const uint32_t* R8, const uint32_t* S8,
+                  const uint32_t* k8, const uint32_t* mode, uint8_t* blob, uint32_t capacity, uint32_t* out1) {
+  if (!g_wc.p || g_wc.bits != kKeyCombNarrow || !ntp::kcomb_cap_ok(capacity) ||
+      !ntp::verify_kc_args_ok(n, kidx, kflags, k8, mode, capacity))
+    return (int)hipErrorInvalidValue;
+  for (uint64_t i = 0; i < n; ++i)
+    if (!ntp::wcomb_scalar_ok<kKeyCombNarrow>(S8 + 8 * i)) return (int)hipErrorInvalidValue;
+  NTP_BEGIN
+  Dev di(&err, kidx, 4 * n), df(&err, kflags, 4 * n), dR(&err, R8, 32 * n), dS(&err, S8, 32 * n), dk(&err, k8, 32 * n),
+      dm(&err, mode, 4 * n), dout(&err, nullptr, 4 * n);
+  DevBlob db(&err, blob, capacity, true);
+  NTP_LAUNCH(k_verify_kc<kKeyCombNarrow>, (const uint32_t*)g_wc.p, di.as<uint32_t>(), df.as<uint32_t>(), dR.as<uint32_t>(),
+             dS.as<uint32_t>(), dk.as<uint32_t>(), dm.as<uint32_t>(), db.d.as<uint32_t>(), capacity, dout.as<uint32_t>())
+  dout.back(out1, 4 * n);
+  db.back();
   return (int)err;
 }
 

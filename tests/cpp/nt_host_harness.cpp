@@ -38,6 +38,7 @@ inline double nth_rcp_model(double b) {
 #include "../../narwhal-tusk_amd/csrc/small_model.hpp"
 #include "nt_probe_items.hpp"
 #include "ktab/host_ktab.hpp"
+#include "kcomb/host_kcomb.hpp"
 
 namespace nt {
 unsigned long long g_fe_mul = 0, g_fe_sq = 0;
@@ -744,6 +745,51 @@ int nthb_ladder_uv3(uint64_t n, const uint32_t* kidx, const uint32_t* R8, const 
   return 0;
 }
 
+// The comb items over HostKComb (kcomb/host_kcomb.hpp) on the caller's comb blob: the layout
+// above, then `capacity` combs and the guard (ntp::kcomb_probe_bytes); same argument lists and
+// the same argument checks as the probe's entry points (1 where the probe returns an error).
+static HostKComb blob_kcomb(uint8_t* blob, uint32_t capacity) {
+  return HostKComb((uint64_t*)(blob + ntp::kKtProbeCtlBytes), ntp::kKtProbeSlots - 1u, blob + ntp::kKtProbePoolOff, capacity,
+                   (uint32_t*)blob, blob + ntp::kcomb_probe_comb_off(capacity));
+}
+int nthb_kcomb_fill(uint64_t n, const uint32_t* A8, uint8_t* blob, uint32_t capacity, uint32_t* slot) {
+  if (!ntp::kcomb_cap_ok(capacity)) return 1;
+  const HostKComb kt = blob_kcomb(blob, capacity);
+  for (uint64_t i = 0; i < n; ++i) {
+    HostATab at;
+    ntp::item_kcomb_fill(i, A8, kt, at, slot, true);
+  }
+  return 0;
+}
+int nthb_kcomb_line(uint64_t n, const uint32_t* A8, const uint32_t* line, uint8_t* blob, uint32_t capacity, uint32_t* out3,
+                    uint32_t* limbs30) {
+  if (!ntp::kcomb_cap_ok(capacity)) return 1;
+  const HostKComb kt = blob_kcomb(blob, capacity);
+  for (uint64_t i = 0; i < n; ++i) ntp::item_kcomb_line(i, A8, line, kt, out3, limbs30);
+  return 0;
+}
+int nthb_kc_picks(uint64_t n, const uint32_t* k8, uint32_t* out65) {
+  if (!ntp::kc_scalars_ok(n, k8)) return 1;
+  uint64_t slots[kKtBucket] = {};
+  uint32_t ctl[4] = {};
+  const HostKComb kt(slots, kKtBucket - 1, nullptr, 0, ctl, nullptr);
+  for (uint64_t i = 0; i < n; ++i) ntp::item_kc_picks(i, k8, kt, out65);
+  return 0;
+}
+int nthb_ladder_kc(uint64_t n, const uint32_t* kidx, const uint32_t* k8, const uint32_t* dead, uint8_t* blob,
+                   uint32_t capacity, uint32_t* out8) {
+  if (!ntp::kcomb_cap_ok(capacity) || !ntp::ladder_kc_args_ok(n, kidx, k8, dead, capacity)) return 1;
+  const HostKComb kt = blob_kcomb(blob, capacity);
+  for (uint64_t i = 0; i < n; ++i) ntp::item_ladder_kc(i, kidx, k8, dead, kt, out8, true);
+  return 0;
+}
+int nthb_compare_one(uint64_t n, const uint32_t* x8, const uint32_t* y8, const uint32_t* z8, const uint32_t* R8,
+                     const uint32_t* mode, uint32_t* out1) {
+  if (!ntp::modes_ok(n, mode)) return 1;
+  for (uint64_t i = 0; i < n; ++i) ntp::item_compare_one(i, x8, y8, z8, R8, mode, out1);
+  return 0;
+}
+
 // How often fe_invert_vt's matrix application comes out negative for the value z (10 limbs),
 // i.e. how often gcd_lincomb_shift takes its negation branch (fe_inv_vt.hpp: about once in
 // 3,000 inversions).  The outer loop of fe_invert_vt is restated here around the header's own
@@ -1009,6 +1055,21 @@ int nthb_key_comb_sum(uint64_t n, const uint32_t* key, const uint32_t* meta, con
     }
   });
   return rc;
+}
+// verify_kc over the comb blob with the live comb set's key 0 as the comb of B: the narrowest
+// width, built of B alone (nthb_wcomb_build), as the probe's entry point asks for it
+int nthb_verify_kc(uint64_t n, const uint32_t* kidx, const uint32_t* kflags, const uint32_t* R8, const uint32_t* S8,
+                   const uint32_t* k8, const uint32_t* mode, uint8_t* blob, uint32_t capacity, uint32_t* out1) {
+  constexpr int W = kKeyCombNarrow;
+  if (g_hwc.bits != W || host_combs<W>().empty() || !ntp::kcomb_cap_ok(capacity) ||
+      !ntp::verify_kc_args_ok(n, kidx, kflags, k8, mode, capacity))
+    return 1;
+  for (uint64_t i = 0; i < n; ++i)
+    if (!ntp::wcomb_scalar_ok<W>(S8 + 8 * i)) return 1;
+  const HostKComb kt(blob_kcomb(blob, capacity));
+  const HostCombRef<HostWComb<W>> wb{&host_combs<W>()[0]};
+  for (uint64_t i = 0; i < n; ++i) ntp::item_verify_kc(i, kidx, kflags, R8, S8, k8, mode, wb, kt, out1, true);
+  return 0;
 }
 // wcomb_fill_target of n threads t of a fill launch over nkeys keys: out = live, key, pos,
 // chunk, dst, tmp (6 words per thread); geom = kPos, kChunks, kEntries, kWordsPerPoint,

@@ -298,6 +298,152 @@ NT_HD NT_INLINE void item_ladder_uv3(size_t i, const uint32_t* kidx, const uint3
   if (write) st_w<8>(out8, i, o);
 }
 
+// ---- the key-table cache's comb path (ed25519_ops.hpp ktab_build_comb, kc_recode / kc_pick,
+// ladder_kc, compare_one, verify_kc).  These items run over a second layout: the blob above,
+// words 8..9 of its control block carrying the comb pool's address, then `capacity` combs of
+// kKtCombBytes, then kKcProbeGuardBytes that nothing may write (the caller prefills pool, combs
+// and guard and reads them back).  The three-table items above keep their blob (words 8..9
+// zero: has_comb() is false there and the window tables are built).
+constexpr size_t kKcProbeGuardBytes = 8192;
+constexpr int kKcPickWords = 65;  // per item of the picks probe: 64 lookups, then c
+inline size_t kcomb_probe_comb_off(uint32_t capacity) { return ktab_probe_bytes(capacity); }
+inline size_t kcomb_probe_bytes(uint32_t capacity) {
+  return kcomb_probe_comb_off(capacity) + (size_t)capacity * kKtCombBytes + kKcProbeGuardBytes;
+}
+static_assert(kKtProbePoolOff % 128 == 0 && kKtEntryBytes % 128 == 0 && kKtCombBytes % 128 == 0,
+              "the comb pool starts on a 128-byte line of the blob");
+// the entry points' argument checks, on the host before anything runs
+inline bool kcomb_cap_ok(uint32_t capacity) { return capacity >= 1 && capacity <= kKtProbeMaxCap; }
+inline bool kc_scalars_ok(uint64_t n, const uint32_t* k8) {  // k < 2^253: bit 255 of W is free
+  for (uint64_t i = 0; i < n; ++i)
+    if (k8[8 * i + 7] >> 29) return false;
+  return true;
+}
+inline bool ladder_kc_args_ok(uint64_t n, const uint32_t* kidx, const uint32_t* k8, const uint32_t* dead,
+                              uint32_t capacity) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (kidx[i] >= capacity || dead[i] > 1u) return false;
+  return kc_scalars_ok(n, k8);
+}
+inline bool modes_ok(uint64_t n, const uint32_t* mode) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (mode[i] > 1u) return false;
+  return true;
+}
+inline bool verify_kc_args_ok(uint64_t n, const uint32_t* kidx, const uint32_t* kflags, const uint32_t* k8,
+                              const uint32_t* mode, uint32_t capacity) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (kidx[i] >= capacity || kflags[i] > (kKtUndecodable | kKtSmallOrder)) return false;
+  return kc_scalars_ok(n, k8) && modes_ok(n, mode);
+}
+
+// The comb of item i's key as verify_n makes it: ktab_probe -> ktab_take -> the four-argument
+// ktab_build with the lane's table workspace.  live = false (a lane past n): no probe, no
+// claim, the build's arithmetic alone.  slot[i] = the index slot won, or kKtNoSlot.
+template <class ATab, class KT>
+NT_HD NT_INLINE void item_kcomb_fill(size_t i, const uint32_t* A8, const KT& kt, ATab& at, uint32_t* slot, bool live) {
+  uint32_t Aw[8];
+  ld_w<8>(Aw, A8, i);
+  uint32_t claim = kKtNoSlot;
+  if (live) {
+    KtProbe p;
+    ktab_probe(p, Aw, kt);
+    claim = ktab_take(p, kt);
+  }
+  ktab_build(Aw, claim, kt, at);
+  if (live) slot[i] = claim;
+}
+// What a reader finds for item i's key: out3 as item_ktab_point's; limbs30 = comb line
+// line[i] of the key's entry through comb_load (a number past 32 goes through comb_line's clamp)
+template <class KT>
+NT_HD NT_INLINE void item_kcomb_line(size_t i, const uint32_t* A8, const uint32_t* line, const KT& kt, uint32_t* out3,
+                                     uint32_t* limbs30) {
+  uint32_t Aw[8];
+  ld_w<8>(Aw, A8, i);
+  KtProbe p;
+  ktab_probe(p, Aw, kt);
+  const uint32_t idx = ktab_ready_index(p, kt);
+  uint32_t same = 0, flags = 0;
+  ge_niels q;
+  fe_0(q.ypx); fe_0(q.ymx); fe_0(q.xy2d);
+  if (idx != kKtNoSlot) {
+    kt.acquire();
+    uint32_t tag[8];
+    kt.hdr_load(idx, tag, flags);
+    same = 1;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) same &= tag[l] == Aw[l];
+    kt.comb_load(idx, line[i], q);
+  }
+  out3[3 * i] = idx;
+  out3[3 * i + 1] = same;
+  out3[3 * i + 2] = flags;
+  uint32_t* o = limbs30 + 30 * i;
+#pragma unroll
+  for (int l = 0; l < 10; ++l) { o[l] = q.ypx.v[l]; o[10 + l] = q.ymx.v[l]; o[20 + l] = q.xy2d.v[l]; }
+}
+// kc_recode of k, then the 64 kc_pick words (entry | negate << 8) in ladder_kc's order --
+// columns 15 .. 0, blocks 0 .. 3 within a column -- and c; the parked W goes through
+// kt.dig_put / dig_get (the device: the LDS digit cells)
+template <class KT>
+NT_HD NT_INLINE void item_kc_picks(size_t i, const uint32_t* k8, const KT& kt, uint32_t* out65) {
+  uint32_t k[8];
+  ld_w<8>(k, k8, i);
+  kc_recode(k, kt);
+  uint32_t* o = out65 + (size_t)kKcPickWords * i;
+  int n = 0;
+  for (uint32_t col = kKcCols; col-- > 0;)
+    for (uint32_t j = 0; j < kKcBlocks; ++j) o[n++] = kc_pick(kt, col, j);
+  o[n] = kt.dig_get(8u);
+}
+// ladder_kc's [k](-A) over the comb of pool entry kidx[i] (dead[i]: the identity); out8 = the encoding
+template <class KT>
+NT_HD NT_INLINE void item_ladder_kc(size_t i, const uint32_t* kidx, const uint32_t* k8, const uint32_t* dead,
+                                    const KT& kt, uint32_t* out8, bool write) {
+  uint32_t k[8], o[8];
+  ld_w<8>(k, k8, i);
+  ge_cp t;
+  ladder_kc(t, k, dead[i], kt, kidx[i]);
+  ge_p2 p;
+  ge_cp_to_p2(p, t);
+  ge_tobytes_w(o, p);
+  if (write) st_w<8>(out8, i, o);
+}
+// compare_one<MODE> of R' = (x z : y z : z) with the encoding R (x, y, z: 8 words each, taken as
+// fe_frombytes_w takes them; z != 0), z inverted by fe_invert_batch, the strict small-order
+// test as verify_kc asks for it; mode 0 strict, 1 cofactorless
+NT_HD NT_INLINE void item_compare_one(size_t i, const uint32_t* x8, const uint32_t* y8, const uint32_t* z8,
+                                      const uint32_t* R8, const uint32_t* mode, uint32_t* out1) {
+  uint32_t xw[8], yw[8], zw[8], Rw[8];
+  ld_w<8>(xw, x8, i);
+  ld_w<8>(yw, y8, i);
+  ld_w<8>(zw, z8, i);
+  ld_w<8>(Rw, R8, i);
+  fe x, y, z, zi;
+  fe_frombytes_w(x, xw);
+  fe_frombytes_w(y, yw);
+  fe_frombytes_w(z, zw);
+  ge_p2 P;
+  fe_mul(P.X, x, z);
+  fe_mul(P.Y, y, z);
+  P.Z = z;
+  fe_invert_batch(zi, z);
+  out1[i] = mode[i] == 0 ? compare_one<kStrict>(P, zi, Rw, true) : compare_one<kCofactorless>(P, zi, Rw, false);
+}
+// verify_kc's bit for (R, S, k) over the comb of pool entry kidx[i], the header flags as given, wb the comb of B
+template <class WComb, class KT>
+NT_HD NT_INLINE void item_verify_kc(size_t i, const uint32_t* kidx, const uint32_t* kflags, const uint32_t* R8,
+                                    const uint32_t* S8, const uint32_t* k8, const uint32_t* mode, const WComb& wb,
+                                    const KT& kt, uint32_t* out1, bool write) {
+  uint32_t Rw[8], Sw[8], k[8];
+  ld_w<8>(Rw, R8, i);
+  ld_w<8>(Sw, S8, i);
+  ld_w<8>(k, k8, i);
+  const uint32_t ok = mode[i] == 0 ? verify_kc<kStrict>(Rw, Sw, k, kflags[i], wb, kt, kidx[i])
+                                   : verify_kc<kCofactorless>(Rw, Sw, k, kflags[i], wb, kt, kidx[i]);
+  if (write) out1[i] = ok;
+}
+
 // ---- the wide combs (ed25519_ops.hpp wcomb_*, wcomb_build.hpp): digits, table entries, sums.
 // A comb type here is the product's WideComb<W> (device), or a host type with the same
 // members: kBits, base, load, load_corr.

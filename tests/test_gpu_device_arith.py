@@ -14,7 +14,10 @@ all five digit widths and read back through WideComb::load entry by entry -- ent
 2^(W-1), entry 0, the reduced comb's extra chunk and its [L](-A) entry, a short last
 fill batch -- with the digit schedule and the sums at chosen scalars: a carry
 through every position, a zero first digit from the identity, waves in which only
-some lanes owe the reduced comb's correction.  tests/test_host_arith.py runs the
+some lanes owe the reduced comb's correction.  The comb path of cached rows runs over
+DevKTab with a comb pool: ktab_build_comb in chosen claim compositions, every comb
+line, kc_recode / kc_pick, ladder_kc with lanes of mixed parity, entry and liveness,
+compare_one and verify_kc at chosen (R, s, k).  tests/test_host_arith.py runs the
 same checks on the host build.  Nothing is compiled here: a missing or stale
 probe library fails at once.
 """
@@ -40,7 +43,7 @@ def host():
     """the host build as build() left it (the half-size reference and the ladder's vectors)"""
     lib = os.path.join(H.CPP, "build", "libnthost.so")
     srcs = [os.path.join(H.CPP, "nt_host_harness.cpp"), os.path.join(H.CPP, "nt_probe_items.hpp"),
-            os.path.join(H.CPP, "ktab", "host_ktab.hpp")] + \
+            os.path.join(H.CPP, "ktab", "host_ktab.hpp"), os.path.join(H.CPP, "kcomb", "host_kcomb.hpp")] + \
         glob.glob(os.path.join(_devprobe.CSRC, "*.hpp"))
     _devprobe.check_fresh(lib, srcs)
     return H.runner("", build=False)
@@ -127,3 +130,27 @@ def test_key_comb_sum_lane_mixed_corrections(dev):
 
 def test_wide_comb_entry_points_refuse_bad_arguments(dev):
     print("comb calls refused: %d" % C.check_wcomb_refusals(dev))
+
+
+def test_key_comb_lines_and_claim_compositions(dev):
+    print("comb lines compared: %d" % C.check_kcomb_tables(dev))
+
+
+def test_comb_recoding_picks(dev):
+    print("pick vectors compared: %d" % C.check_kc_picks(dev))
+
+
+def test_comb_ladder_lane_mixed_parity_entry_and_dead(dev):
+    print("comb ladder results compared: %d" % C.check_ladder_kc(dev))
+
+
+def test_compare_one_chosen_points(dev):
+    print("compare_one bits compared: %d" % C.check_compare_one(dev))
+
+
+def test_verify_kc_chosen_scalars(dev):
+    print("verify_kc verdicts compared: %d" % C.check_verify_kc(dev))
+
+
+def test_comb_entry_points_refuse_bad_arguments(dev):
+    print("comb-path calls refused: %d" % C.check_kcomb_refusals(dev))

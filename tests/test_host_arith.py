@@ -135,6 +135,42 @@ def test_wide_comb_entry_points_refuse_bad_arguments(host):
     print("comb calls refused: %d" % C.check_wcomb_refusals(host))
 
 
+def test_key_comb_lines_and_claim_compositions(host):
+    """ktab_build with a comb pool over HostKComb, every line against the point model"""
+    print("comb lines compared: %d" % C.check_kcomb_tables(host))
+
+
+def test_comb_recoding_picks(host):
+    print("pick vectors compared: %d" % C.check_kc_picks(host))
+
+
+def test_comb_ladder_lane_mixed_parity_entry_and_dead(host):
+    print("comb ladder results compared: %d" % C.check_ladder_kc(host))
+
+
+def test_compare_one_chosen_points(host):
+    print("compare_one bits compared: %d" % C.check_compare_one(host))
+
+
+def test_verify_kc_chosen_scalars(host):
+    print("verify_kc verdicts compared: %d" % C.check_verify_kc(host))
+
+
+def test_comb_entry_points_refuse_bad_arguments(host):
+    print("comb-path calls refused: %d" % C.check_kcomb_refusals(host))
+
+
+def test_comb_items_under_the_sanitizers():
+    """The stand-alone program (its own main, -fsanitize=address,undefined, run directly): the
+    probe's comb items over HostKComb on exact-size heap allocations, the key set of
+    ktab_items_check with room for every key and with a pool of 4."""
+    import subprocess
+    subprocess.run(["make", "-s", "-C", H.CPP, "build/kcomb_items_check"], check=True)
+    r = subprocess.run([os.path.join(H.CPP, "build", "kcomb_items_check")], capture_output=True, text=True)
+    print(r.stdout.strip())
+    assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
+
+
 def _fill_targets(bits, nkeys, t):
     """wcomb_fill_target of the threads t: (live, key, pos, chunk, dst, tmp) columns and the width's
     geometry (kPos, kChunks, kEntries, kWordsPerPoint, kCorrWord, comb / bases / tmp bytes per key, batch)"""
@@ -212,7 +248,7 @@ def test_device_probe_exports_every_entry():
     lib = _devprobe.load()
     for sym in _devprobe.EXPORTS:
         getattr(lib, sym)
-    assert len(_devprobe.EXPORTS) == 28
+    assert len(_devprobe.EXPORTS) == 34
     lib.ntp_key_sort  # device-only: the product's counting sort (csrc/key_sort.hpp), no host twin
 
 

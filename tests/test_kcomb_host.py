@@ -63,34 +63,9 @@ def corpus_keys(corpus):
     return out
 
 
-class Mul:
-    """[k]Q for many k and one Q of the integer/point model: the powers [2^i]Q once, then additions"""
-
-    def __init__(self, M, Q):
-        self.M, self.pw = M, [Q]
-        for _ in range(255):
-            self.pw.append(M.padd(self.pw[-1], self.pw[-1]))
-
-    def __call__(self, k):
-        acc = self.M.IDENT
-        i = 0
-        while k:
-            if k & 1:
-                acc = self.M.padd(acc, self.pw[i])
-            k >>= 1
-            i += 1
-        return acc
-
-
 def affine(M, p):
     zi = M.inv(p[2])
     return p[0] * zi % P, p[1] * zi % P
-
-
-def entry_scalar(block, index):
-    """the integer multiple of A that line 8 block + index holds"""
-    r = [1 if index >> t & 1 else -1 for t in range(3)]
-    return (1 << 16 * block) * ((1 << 192) + r[2] * (1 << 128) + r[1] * (1 << 64) + r[0])
 
 
 def test_recoding_rebuilds_k_exactly(lib):
@@ -110,7 +85,7 @@ def test_recoding_rebuilds_k_exactly(lib):
             assert block == i % 4, (hex(k), i)
             if i % 4 == 0 and i:
                 acc *= 2
-            acc += (1 if neg else -1) * entry_scalar(block, index)
+            acc += (1 if neg else -1) * C.entry_scalar(block, index)
         assert c == 1 - (k & 1) and acc == k + c, hex(k)
 
 
@@ -137,9 +112,9 @@ def test_table_bytes(lib, corpus, kind):
     assert (comb[:idx * COMB] == 0xA5).all() and (comb[(idx + 1) * COMB:] == 0xA5).all()
     lines = comb[idx * COMB:(idx + 1) * COMB].reshape(33, LINE)
     assert (lines[:, 120:] == 0xA5).all()
-    mul = Mul(M, A)
+    mul = C.Mul(A)
     for n in range(33):
-        pt = A if n == 32 else mul(entry_scalar(n // 8, n % 8))
+        pt = A if n == 32 else mul(C.entry_scalar(n // 8, n % 8))
         w = lines[n, :120].view(np.uint32).reshape(3, 10)
         got = tuple(C.value([int(v) for v in w[c]]) % P for c in range(3))
         assert got == _niels(M, pt), (kind, n)
@@ -176,7 +151,7 @@ def test_ladder_kc_against_the_point_model(lib, corpus, kind):
     that its key is dead gets the identity."""
     M = C.model()
     e, A = corpus_keys(corpus)[kind]
-    mul = Mul(M, M.pneg(A))
+    mul = C.Mul(M.pneg(A))
     ks = ladder_scalars()
     assert {k & 1 for k in ks[:9]} == {0, 1}
     out = ctypes.create_string_buffer(32)

@@ -103,32 +103,13 @@ def test_recoding_top_digit_absorbs_the_carry(lib):
         assert sum(x << (4 * i) for i, x in enumerate(d)) == k, hex(k)
 
 
-class Mul:
-    """[k]Q for many k and one Q of the integer/point model: the powers [2^i]Q once, then additions"""
-
-    def __init__(self, M, Q):
-        self.M, self.pw = M, [Q]
-        for _ in range(255):
-            self.pw.append(M.padd(self.pw[-1], self.pw[-1]))
-
-    def __call__(self, k):
-        acc = self.M.IDENT
-        i = 0
-        while k:
-            if k & 1:
-                acc = self.M.padd(acc, self.pw[i])
-            k >>= 1
-            i += 1
-        return acc
-
-
 @pytest.mark.parametrize("kind", ("honest", "mixed", "small"))
 def test_ladder_k4_against_the_point_model(lib, corpus, kind):
     """ladder_k4 = [k](-A) for the edge scalars, the string boundaries and 2,000 seeded random k;
     a lane told that its key is dead gets the identity."""
     M = C.model()
     e, A = corpus_keys(corpus)[kind]
-    mul = Mul(M, M.pneg(A))
+    mul = C.Mul(M.pneg(A))
     assert M.peq(mul(L - 1), M.pmul(L - 1, M.pneg(A)))  # the helper against the model's own multiply
     out = ctypes.create_string_buffer(32)
     for k in ladder_scalars():
