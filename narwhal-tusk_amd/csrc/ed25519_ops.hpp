@@ -5,7 +5,11 @@
 //          (load_signed: entry e0 + |d|, negated when d < 0)
 //   WComb: load(pos, idx, ge_niels&)                            idx * 2^(16 pos) * P (wide comb)
 //   XCache: load(slot, words) / store(slot, words)              decompressed x of keys seen before (NoXCache: none)
-//   KTab:   the window tables of A, [2^64]A, [2^128]A of keys seen before (NoKTab: none; see KTab below)
+//   KTab:   precomputed multiples of keys seen before, kept across calls (NoKTab: none).  The
+//           storage and policy contract and the index protocol are in ktab.hpp; what a cached
+//           row runs is in ktab_comb.hpp (the key's comb: the default) and ktab_tables.hpp (the
+//           three- and four-table generations: A/B builds, harnesses, the device probe); the
+//           gate and the dispatch (ktab_build, verify_one_kt, verify_n) are here.
 //
 // Semantics (restated from ed25519-dalek 1.0.1 /
 // curve25519-dalek 3.x):
@@ -101,14 +105,10 @@ NT_HD NT_INLINE int32_t wcomb_digit(uint32_t d[8], uint32_t& carry, bool top_uns
 // taken as the starting point instead of added to the identity).  The table
 // load of digit i+1 is issued right after the multiplies that consume entry i,
 // so its latency (a random 128-B line) overlaps the rest of the addition.
-#ifndef NT_COMB_FROM_ID
-#define NT_COMB_FROM_ID 1
-#endif
-template <class WComb, bool kFromIdentity = false, int kSkipTop = 0>
+template <class WComb, bool kFromIdentity = false>
 NT_HD NT_INLINE void wcomb_acc(ge_p3& acc, const uint32_t x[8], const WComb& wc, uint32_t neg_all = 0) {
-  // kSkipTop > 0: timing-only experiment builds (wrong results) that drop top positions
   // neg_all: acc += [-x]P (a reduced-scalar comb's k - L < 0): every digit's sign flipped
-  constexpr int W = WComb::kBits, P = CombGeom<W>::kPos - kSkipTop;
+  constexpr int W = WComb::kBits, P = CombGeom<W>::kPos;
   constexpr bool kRed = CombGeom<W>::kReduced;
   uint32_t d[8], carry = 0;
 #pragma unroll
@@ -117,14 +117,12 @@ NT_HD NT_INLINE void wcomb_acc(ge_p3& acc, const uint32_t x[8], const WComb& wc,
   ge_niels ne;
   wc.load(0, (uint32_t)(dg < 0 ? -dg : dg), ne);
   int pos0 = 0;
-  if (kFromIdentity && NT_COMB_FROM_ID) {
+  if (kFromIdentity) {
     ge_niels_cneg(ne, (dg < 0) ^ (neg_all != 0));
     ge_p3_from_niels(acc, ne);
     dg = wcomb_digit<W>(d, carry, kRed && P == 2);
     wc.load(1, (uint32_t)(dg < 0 ? -dg : dg), ne);
     pos0 = 1;
-  } else if (kFromIdentity) {
-    ge_p3_0(acc);  // -DNT_COMB_FROM_ID=0 (A/B builds): add the first entry to the identity
   }
 #pragma unroll 1
   for (int pos = pos0; pos < P; ++pos) {
@@ -300,9 +298,6 @@ NT_HD NT_INLINE void wcomb_fill(uint32_t* dst, uint32_t* tmp, const uint32_t* ba
 constexpr uint32_t kTabR = 9;  // first entry of the R table
 
 // store j * (neg ? -P : P), j = 0..8, at entries e0 .. e0+8
-#ifndef NT_TAB_DBL
-#define NT_TAB_DBL 1
-#endif
 template <class ATab>
 NT_HD NT_INLINE void ptab_build(const ge_p3& P, uint32_t neg, ATab& at, uint32_t e0) {
   ge_p3 Q;
@@ -322,7 +317,6 @@ NT_HD NT_INLINE void ptab_build(const ge_p3& P, uint32_t neg, ATab& at, uint32_t
   at.store(e0, c0);
   ge_p3_to_cached(c1, Q);
   at.store(e0 + 1, c1);
-#if NT_TAB_DBL
   // 2Q, 4Q, 8Q by doubling (4S + 4M each instead of an 8M addition); right after
   // each, its odd neighbour from the point still in registers: 3Q = 2Q + Q,
   // 5Q = 4Q + Q, 7Q = 8Q - Q, and finally 6Q = 7Q - Q (no table reloads:
@@ -353,18 +347,6 @@ NT_HD NT_INLINE void ptab_build(const ge_p3& P, uint32_t neg, ATab& at, uint32_t
     ge_p3_to_cached(c, nb);
     at.store(e0 + 6, c);
   }
-#else
-  ge_p3 cur = Q;
-#pragma unroll 1
-  for (uint32_t j = 2; j < 9; ++j) {
-    ge_cp t;
-    ge_add_cached(t, cur, c1);
-    ge_cp_to_p3(cur, t);
-    ge_cached cj;
-    ge_p3_to_cached(cj, cur);
-    at.store(e0 + j, cj);
-  }
-#endif
 }
 
 // any lane of the wave (the host: this lane)
@@ -504,20 +486,9 @@ NT_HD NT_INLINE uint32_t compare_one(const ge_p2& P, const fe& zi, const uint32_
 }
 
 // The inversion of a key-cache batch (verification is public data): the
-// variable-time binary GCD (fe_inv_vt.hpp) unless -DNT_INV_VT=0 (the Fermat
-// chain, 254 squarings + 11 multiplies).
-#ifndef NT_INV_VT
-#define NT_INV_VT 1
-#endif
-NT_HD NT_INLINE void fe_invert_batch(fe& out, const fe& z) {
-#if defined(NT_EXPERIMENT_NO_INV)
-  out = z;  // timing only (wrong verdicts): what the batch inversion costs a launch
-#elif NT_INV_VT
-  fe_invert_vt(out, z);
-#else
-  fe_invert(out, z);
-#endif
-}
+// variable-time binary GCD (fe_inv_vt.hpp), not the Fermat chain (fe_invert:
+// 254 squarings + 11 multiplies).
+NT_HD NT_INLINE void fe_invert_batch(fe& out, const fe& z) { fe_invert_vt(out, z); }
 
 // ---------------------------------------------------------------------------
 // The x cache: a public key's decompressed x, kept across calls in a table of
@@ -685,482 +656,16 @@ NT_HD NT_INLINE uint32_t verify_uv(const uint32_t Aw[8], const uint32_t Rw[8], c
   return ok & fe_iszero(acc.X) & fe_eq(acc.Y, acc.Z);
 }
 
-// ---------------------------------------------------------------------------
-// The key-table cache (KTab): for a public key this context has seen before,
-// the window tables j * P, j = 1..8, of P = A, A' = [2^64]A and A'' = [2^128]A,
-// kept across calls.  With them the lattice vector need not be balanced:
-// |u| ~ 2^192, v ~ 2^64 (sc_unbalanced), the 4-bit digits of |u| split into three
-// strings of 16 over the three tables, and the joint ladder is ~17 windows of
-// 4 doublings + 4 additions instead of ~33 of 4 + 2 (verify_uv3).  [u]A =
-// [u0]A + [u1]A' + [u2]A'' is an integer identity (A', A'' come from real
-// doublings of A), so the verdict is verify_uv's for every input.
-// What the product runs on a cached row is further down: a fourth table (verify_k4) or, the
-// default, the key's comb in the second pool (verify_kc); the three tables are then not built.
-//
-// Storage (the verify kernel: DevKTab, kernels_common.hpp; the host harness: plain
-// memory and host atomics):
-//   pool   entries of kKtEntryBytes: a 128-B header (the 32 key bytes as tag,
-//          kKt* flags) + 3 tables x 8 cached points of 160 B.  Insert-only: an
-//          entry is handed out once by a bump counter and never rewritten or
-//          freed while the context lives.
-//   index  8-byte slots {fingerprint32, state32}; a key has two buckets of
-//          kKtBucket slots (half a 128-B line each) from two hashes.
-//   state  0 empty -> kKtSeen (first sighting: one CAS, nothing else)
-//          -> kKtClaimed (second sighting: CAS, one winner per key, who builds
-//          the entry after its verification) -> kKtReady0 + entry index.
-//          Pool exhausted: the slot stays kKtSeen.
-// Soundness.  A pool line is never read before the slot that names it has been
-// read as ready, the builder stores the whole entry, drains, releases at agent
-// scope and only then stores the slot word, and the reader acquires at agent
-// scope between the slot loads and the first pool load: together with
-// insert-only this means a reader sees either no entry or the finished one.  A
-// stale slot read is only a miss.  The header's full 32-byte tag is compared
-// before a table is used, so a fingerprint collision is a miss as well, and
-// every index is masked (slots) or bounds-checked (entries) before use.
-// A wave row takes the fast path only when all its lanes hit.
-//
-// Policy (KT):
-//   kEnabled, active(), slot_mask() (slots - 1, a power of two >= kKtBucket),
-//   capacity() (entries), slot_load / slot_cas / slot_store / slot_publish,
-//   acquire(), drain_release(), pool_used(), pool_take(), hdr_load / hdr_store,
-//   tab_store(idx, t, j, c), tab_load_signed(idx, t, d, c), count(which),
-//   claim_put / claim_get (what a lane owes the cache after its row, parked outside
-//   its registers while the balanced path runs), dig_put / dig_get (the 16 digit
-//   words of the three-table ladder, likewise; the comb's ladder parks its 9 there)
-// and, for the policies that say so, the fourth table's or the comb's accessors (below).
-// ---------------------------------------------------------------------------
-constexpr uint32_t kKtTables = 3, kKtPerTable = 8;
-constexpr uint32_t kKtHeaderBytes = 128, kKtPointBytes = 160;
-constexpr uint32_t kKtEntryBytes = kKtHeaderBytes + kKtTables * kKtPerTable * kKtPointBytes;  // 3,968
-constexpr uint32_t kKtBucket = 8;             // slots per bucket (64 bytes)
-constexpr uint32_t kKtCand = 2 * kKtBucket;   // slots a probe reads
-constexpr uint32_t kKtSeen = 1, kKtClaimed = 2, kKtReady0 = 16;  // slot states; ready: kKtReady0 + index
-constexpr uint32_t kKtNoSlot = 0xffffffffu;
-constexpr uint32_t kKtWantMark = 0xfffffffeu;  // parked beside a claimed slot: mark this key after the row
-constexpr uint32_t kKtWantTake = 0xfffffffdu;  // ... or claim it outright: the x cache has met it before
-constexpr uint32_t kKtFlagShift = 28, kKtMaxEntries = 1u << kKtFlagShift;  // entry index | flags in one word
-enum : uint32_t { kKtUndecodable = 1u, kKtSmallOrder = 2u };  // header flags
-enum { kKtCntFast = 0, kKtCntBuild = 1, kKtCntOld = 2 };      // counters: wave rows
+}  // namespace nt
 
-// The fourth table, A''' = [2^192]A, lives outside the entry, in an extension pool
-// of kKtExtBytes per entry index (8 cached points: ten 128-B lines).  With it the
-// whole 253-bit k splits into four strings of 16 digits and the cached verify needs
-// no lattice vector and nothing of R but its bytes (verify_k4).  A policy says that
-// it can carry one with `static constexpr bool kExt = true` and then has
-//   has_ext() (wave-uniform: an extension pool is there), ext_store(idx, j, c),
-//   ext_load_signed(idx, d, c)
-// Policies without the member are three-table policies: nothing below asks them for more.
-constexpr uint32_t kKtExtBytes = kKtPerTable * kKtPointBytes;  // 1,280
-template <class KT>
-constexpr auto kt_ext_of(int) -> decltype(KT::kExt) { return KT::kExt; }
-template <class KT>
-constexpr bool kt_ext_of(long) { return false; }
-template <class KT>
-constexpr bool kKtHasExt = kt_ext_of<KT>(0);
-// an extension pool is there (wave-uniform)
-template <class KT>
-NT_HD NT_INLINE bool ktab_has_ext(const KT& kt) {
-  if constexpr (kKtHasExt<KT>) return kt.has_ext();
-  else return false;
-}
+// The key-table cache: contract and index protocol, then its generations (see the top of
+// this file); their callers follow.
+#include "ktab.hpp"
+#include "ktab_tables.hpp"
+#include "ktab_comb.hpp"
 
-// The comb.  The second pool may instead hold, per entry index, a Lim-Lee comb of A with
-// kKcTeeth = 4 teeth 64 bits apart and kKcBlocks = 4 blocks of kKcCols = 16 columns: 33 affine
-// niels entries (y+x, y-x, 2dxy), one 128-B line each (120 B used), kKtCombBytes per key.
-//   entry 8 j + e   2^(16 j) (2^192 + r2 2^128 + r1 2^64 + r0) A,  r_t = +1 if bit t of e is set, else -1
-//   entry 32        A itself
-// With K = k | 1 and W = (K >> 1) | 2^255, the signs s_i = 2 bit_i(W) - 1 give
-// sum s_i 2^i = 2 W - (2^256 - 1) = K as an INTEGER, so [K]A is the sum of 64 signed entries
-// for every A, torsion component or not: column `col` of block j takes bits 16 j + col of the
-// four 64-bit limbs of W, the top tooth's sign factored out (ladder_kc: 15 doublings, 64
-// mixed additions, and one more of entry 32 or the identity for the parity of k).  A policy
-// says that it can carry one with `static constexpr bool kComb = true` and then has
-//   has_comb() (wave-uniform: the second pool is there and holds combs),
-//   comb_store(idx, entry, niels), comb_load(idx, entry, niels&)
-// Only the entry's 128-B header is written beside a comb: no window table is built.
-constexpr uint32_t kKcTeeth = 4, kKcBlocks = 4, kKcCols = 16, kKcPerBlock = 1u << (kKcTeeth - 1);
-constexpr uint32_t kKcSigned = kKcBlocks * kKcPerBlock;  // 32 signed entries, then +A
-constexpr uint32_t kKcEntries = kKcSigned + 1, kKcLineBytes = 128;
-constexpr uint32_t kKtCombBytes = kKcEntries * kKcLineBytes;  // 4,224
-static_assert(kKcTeeth * kKcBlocks * kKcCols == 256 && kKcBlocks * kKcCols == 64,
-              "a tooth is one 64-bit limb of W; the recoding below is written for four of them");
-template <class KT>
-constexpr auto kt_comb_of(int) -> decltype(KT::kComb) { return KT::kComb; }
-template <class KT>
-constexpr bool kt_comb_of(long) { return false; }
-template <class KT>
-constexpr bool kKtHasComb = kt_comb_of<KT>(0);
-// the second pool is there and holds combs (wave-uniform)
-template <class KT>
-NT_HD NT_INLINE bool ktab_has_comb(const KT& kt) {
-  if constexpr (kKtHasComb<KT>) return kt.has_comb();
-  else return false;
-}
+namespace nt {
 
-// What a row whose lanes all hit runs, by what the policy carries and which pools are there
-// (wave-uniform, and the same for every launch of a context): the comb's ladder (verify_kc), the
-// four-table ladder (verify_k4), the three-table ladder over the unbalanced vector (verify_uv3),
-// or nothing -- a policy that can carry a fourth table has none of them without its second pool.
-// The gate and the dispatch of verify_one_kt both ask here.
-enum : uint32_t { kKtFastNone = 0, kKtFastThree = 3, kKtFastFour = 4, kKtFastComb = 5 };
-template <class KT>
-NT_HD NT_INLINE uint32_t ktab_fast_kind(const KT& kt) {
-  if constexpr (kKtHasComb<KT>) {
-    if (kt.has_comb()) return kKtFastComb;
-  }
-  if constexpr (kKtHasExt<KT>) return kt.has_ext() ? kKtFastFour : kKtFastNone;
-  else return kKtFastThree;
-}
-
-struct NoKTab {
-  static constexpr bool kEnabled = false;
-  NT_HD NT_INLINE bool active() const { return false; }
-  NT_HD NT_INLINE uint32_t slot_mask() const { return 0; }
-  NT_HD NT_INLINE uint32_t capacity() const { return 0; }
-  NT_HD NT_INLINE uint64_t slot_load(uint32_t) const { return 0; }
-  NT_HD NT_INLINE uint64_t slot_cas(uint32_t, uint64_t, uint64_t) const { return ~0ull; }  // returns the old word
-  NT_HD NT_INLINE void dig_put(uint32_t, uint32_t) const {}
-  NT_HD NT_INLINE uint32_t dig_get(uint32_t) const { return 0; }
-  NT_HD NT_INLINE void claim_put(uint32_t) const {}
-  NT_HD NT_INLINE uint32_t claim_get() const { return 0xffffffffu; }
-  NT_HD NT_INLINE void slot_store(uint32_t, uint64_t) const {}
-  NT_HD NT_INLINE void slot_publish(uint32_t, uint64_t) const {}
-  NT_HD NT_INLINE void acquire() const {}
-  NT_HD NT_INLINE void drain_release() const {}
-  NT_HD NT_INLINE uint32_t pool_used() const { return 0; }
-  NT_HD NT_INLINE uint32_t pool_take() const { return 0; }
-  NT_HD NT_INLINE void hdr_load(uint32_t, uint32_t*, uint32_t&) const {}
-  NT_HD NT_INLINE void hdr_store(uint32_t, const uint32_t*, uint32_t) const {}
-  NT_HD NT_INLINE void tab_store(uint32_t, uint32_t, uint32_t, const ge_cached&) const {}
-  NT_HD NT_INLINE void tab_load_signed(uint32_t, uint32_t, int32_t, ge_cached&) const {}
-  NT_HD NT_INLINE void count(int) const {}
-};
-
-// a key's fingerprint in its index slot
-NT_HD NT_INLINE uint32_t ktab_fp(const uint32_t Aw[8]) { return xcache_hash(Aw, 0x94d049bbu); }
-NT_HD NT_INLINE uint64_t ktab_word(uint32_t fp, uint32_t st) { return (uint64_t)fp | ((uint64_t)st << 32); }
-
-// What a probe found: the key's fingerprint, the state and slot of its match
-// (st = 0: none) and the empty slots a first sighting may take: bit c of `ord` =
-// slot c of the emptier bucket (base pb), bit 8 + c = slot c of the other (base
-// ob); ord = 0: both buckets full -- the key stays homeless.
-struct KtProbe {
-  uint32_t fp, st, slot, pb, ob, ord;
-};
-
-// 16 relaxed slot loads (two buckets of 8: two rounds of loads in flight together)
-template <class KT>
-NT_HD NT_INLINE void ktab_probe(KtProbe& p, const uint32_t Aw[8], const KT& kt) {
-  const uint32_t mask = kt.slot_mask(), bm = mask / kKtBucket;
-  const uint32_t b0 = (xcache_hash(Aw, 0x51ed270bu) & bm) * kKtBucket;
-  const uint32_t b1 = (xcache_hash(Aw, 0x2545f491u) & bm) * kKtBucket;
-  p.fp = ktab_fp(Aw);
-  p.st = 0;
-  p.slot = 0;
-  uint64_t w[kKtCand];
-#pragma unroll
-  for (uint32_t c = 0; c < kKtCand; ++c) w[c] = kt.slot_load(((c < kKtBucket ? b0 : b1) | (c & (kKtBucket - 1))) & mask);
-  uint32_t emp = 0;
-#pragma unroll
-  for (uint32_t c = 0; c < kKtCand; ++c) {
-    const uint32_t hi = (uint32_t)(w[c] >> 32);
-    emp |= (w[c] == 0 ? 1u : 0u) << c;
-    if (hi != 0 && (uint32_t)w[c] == p.fp && hi > p.st) {  // the furthest state wins (a key marked twice)
-      p.st = hi;
-      p.slot = ((c < kKtBucket ? b0 : b1) | (c & (kKtBucket - 1))) & mask;
-    }
-  }
-  // two-choice placement: the emptier bucket first
-  const uint32_t e0 = emp & ((1u << kKtBucket) - 1u), e1 = emp >> kKtBucket;
-  const bool second = __builtin_popcount(e1) > __builtin_popcount(e0);
-  p.pb = second ? b1 : b0;
-  p.ob = second ? b0 : b1;
-  p.ord = second ? (e1 | (e0 << kKtBucket)) : (e0 | (e1 << kKtBucket));
-}
-
-// The entry index of a ready match below the launch's capacity; kKtNoSlot otherwise.
-template <class KT>
-NT_HD NT_INLINE uint32_t ktab_ready_index(const KtProbe& p, const KT& kt) {
-  const uint32_t idx = p.st - kKtReady0;
-  return (p.st >= kKtReady0 && idx < kt.capacity()) ? idx : kKtNoSlot;
-}
-
-// The mark of a key that has no slot (p.st == 0): kKtSeen by CAS into the first slot the
-// probe saw empty.  A mark that loses its CAS to another key (a batch of new keys fills its
-// buckets at once) takes the next slot the probe saw empty, three tries in all and nothing
-// re-read; one that loses to a lane with the same key is done.
-// A mark is a partial write to a line no cache holds, acknowledged from the memory side, and
-// the wave waits for it with its next loads: a launch whose every lane marks at once queues
-// ~1.5 ns per mark behind one another (measured: 200 k marks, +0.3 ms).
-// So a key the x cache meets for the first time writes nothing here -- that sighting is
-// recorded for nothing by the x cache, which stores the key's x then -- and a key the x cache
-// has met before is claimed outright and built (ktab_take); only keys of which the x cache can
-// say nothing go through the mark (ge_frombytes_cached's `seen`).  Keys that never come back
-// never pay.
-template <class KT>
-NT_HD NT_INLINE void ktab_mark(const KtProbe& p, const KT& kt) {
-  uint32_t ord = p.ord;
-#pragma unroll 1
-  for (int a = 0; a < 3 && ord != 0; ++a) {
-    const uint32_t c = (uint32_t)__builtin_ctz(ord);
-    ord &= ord - 1u;
-    const uint32_t i = ((c < kKtBucket ? p.pb : p.ob) | (c & (kKtBucket - 1))) & kt.slot_mask();
-    const uint64_t old = kt.slot_cas(i, 0, ktab_word(p.fp, kKtSeen));
-    if (old == 0 || (uint32_t)old == p.fp) break;
-  }
-}
-// The claim of a key marked before: returns 1 for the one winner of the CAS, who builds the
-// entry after its verification (ktab_build).  A claimed or ready slot and a full pool are left
-// as they are.
-template <class KT>
-NT_HD NT_INLINE uint32_t ktab_claim(const KtProbe& p, const KT& kt) {
-  if (p.st == kKtSeen && kt.pool_used() < kt.capacity())
-    return kt.slot_cas(p.slot, ktab_word(p.fp, kKtSeen), ktab_word(p.fp, kKtClaimed)) == ktab_word(p.fp, kKtSeen) ? 1u : 0u;
-  return 0;
-}
-// A slot for a key that has none, claimed outright (the x cache vouches for an earlier
-// meeting): returns the slot won, kKtNoSlot otherwise.
-template <class KT>
-NT_HD NT_INLINE uint32_t ktab_take(const KtProbe& p, const KT& kt) {
-  if (p.st != 0) return ktab_claim(p, kt) ? p.slot : kKtNoSlot;
-  if (kt.pool_used() >= kt.capacity()) return kKtNoSlot;
-  uint32_t ord = p.ord;
-#pragma unroll 1
-  for (int a = 0; a < 3 && ord != 0; ++a) {
-    const uint32_t c = (uint32_t)__builtin_ctz(ord);
-    ord &= ord - 1u;
-    const uint32_t i = ((c < kKtBucket ? p.pb : p.ob) | (c & (kKtBucket - 1))) & kt.slot_mask();
-    const uint64_t old = kt.slot_cas(i, 0, ktab_word(p.fp, kKtClaimed));
-    if (old == 0) return i;
-    if ((uint32_t)old == p.fp) break;
-  }
-  return kKtNoSlot;
-}
-// Mark or claim in one, for a caller that has no x cache to ask.
-template <class KT>
-NT_HD NT_INLINE uint32_t ktab_sight(const KtProbe& p, const KT& kt) {
-  if (p.st == 0) {
-    ktab_mark(p, kt);
-    return 0;
-  }
-  return ktab_claim(p, kt);
-}
-// ge_frombytes_cached's `seen` for a lane parked as kKtWantMark: a key the x cache meets for
-// the first time is not marked this time
-template <class KT>
-struct KtSeenSink {
-  const KT& kt;
-  NT_HD NT_INLINE void operator()(uint32_t known) const {
-    if (KT::kEnabled && known != 1u && kt.claim_get() == kKtWantMark) kt.claim_put(known ? kKtWantTake : kKtNoSlot);
-  }
-};
-
-// ATab-shaped store adaptor of ptab_build: entries 1..8 of table t of pool entry idx
-// (t = kKtTables: the extension's table)
-template <class KT>
-struct KtStore {
-  const KT& kt;
-  uint32_t idx, t, on;
-  NT_HD NT_INLINE void store(uint32_t entry, const ge_cached& c) {
-    if (!on || entry == 0) return;
-    if constexpr (kKtHasExt<KT>) {
-      if (t >= kKtTables) {
-        kt.ext_store(idx, entry, c);
-        return;
-      }
-    }
-    kt.tab_store(idx, t, entry, c);
-  }
-};
-
-// Build and publish the entries of the lanes with claim != kKtNoSlot (their keys' index slots).  Wave-uniform:
-// every lane of the row runs the arithmetic (on its own key), only the claimers
-// store.  128 doublings and three ptab_builds in a rolled loop, once per key; with an
-// extension pool one round more (192 doublings, four ptab_builds), the fourth table
-// stored like the others before the drain: all of an entry's lines, then drain, release,
-// drain, then the slot word.  Without one (a null extension address, or a three-table
-// policy) exactly the three tables are built and nothing else is stored.
-// Undecodable keys get the header alone, with the flag (the full tag makes a
-// negative entry safe); small-order keys get the flag beside their tables.
-template <class KT>
-NT_HD NT_INLINE void ktab_build(const uint32_t Aw[8], uint32_t claim, const KT& kt) {
-  const uint32_t fp = ktab_fp(Aw);
-  uint32_t idx = 0, have = 0;
-  if (claim != kKtNoSlot) {
-    idx = kt.pool_take();
-    have = idx < kt.capacity() ? 1u : 0u;
-    if (!have) kt.slot_store(claim, ktab_word(fp, kKtSeen));  // pool exhausted: seen for good
-  }
-  ge_p3 P;
-  const uint32_t ok = ge_frombytes_w(P, Aw);
-  const uint32_t flags = (ok ? 0u : kKtUndecodable) | (ge_is_small_order_affine(P) ? kKtSmallOrder : 0u);
-  KtStore<KT> st{kt, idx, 0, have & ok};
-  const uint32_t ntab = kKtTables + (ktab_has_ext(kt) ? 1u : 0u);
-#pragma unroll 1
-  for (uint32_t t = 0; t < ntab; ++t) {
-    st.t = t;
-    ptab_build(P, 0u, st, 0);
-    if (t + 1 < ntab) {
-      ge_p2 q;
-      ge_p3_to_p2(q, P);
-#pragma unroll 1
-      for (int r = 0; r < 63; ++r) ge_dbl_p2(q, q);
-      ge_cp c;
-      ge_dbl(c, q);
-      ge_cp_to_p3(P, c);
-    }
-  }
-  if (have) kt.hdr_store(idx, Aw, flags);
-  // every storing wave drains and releases before any slot word names its entry
-  kt.drain_release();
-  if (have) kt.slot_publish(claim, ktab_word(fp, kKtReady0 + idx));
-}
-
-// The comb's build parks its 16 bases in entries 0 .. 15 of the lane's table workspace.  Every
-// ATab that verify_uv takes holds the two window tables of the balanced path, entries
-// 0 .. kTabR + 8; a policy that states its size (`static constexpr uint32_t kEntries`) is checked
-// against the 16 as well.
-constexpr uint32_t kKcBases = kKcTeeth * kKcBlocks;
-static_assert(kKcBases <= kTabR + 9, "the comb's bases wait in the balanced path's table workspace");
-template <class ATab>
-constexpr auto atab_entries_of(int) -> decltype(ATab::kEntries) { return ATab::kEntries; }
-template <class ATab>
-constexpr uint32_t atab_entries_of(long) { return kTabR + 9; }
-// four field elements parked in one entry of the lane's table workspace (ATab::store / load
-// move a ge_cached as it is): a p3 point, or a cached one
-template <class ATab>
-NT_HD NT_INLINE void kc_park_p3(ATab& at, uint32_t entry, const ge_p3& p) {
-  const ge_cached c{p.X, p.Y, p.Z, p.T};
-  at.store(entry, c);
-}
-template <class ATab>
-NT_HD NT_INLINE void kc_take_p3(const ATab& at, uint32_t entry, ge_p3& p) {
-  ge_cached c;
-  at.load(entry, c);
-  p.X = c.YpX; p.Y = c.YmX; p.Z = c.Z2; p.T = c.T2d;
-}
-// comb line `entry` of pool entry idx for a lane that stores (on), nothing and zeros otherwise
-template <class KT>
-NT_HD NT_INLINE void kc_line_put(const KT& kt, uint32_t idx, uint32_t entry, const ge_niels& q, uint32_t on) {
-  if (on) kt.comb_store(idx, entry, q);
-}
-template <class KT>
-NT_HD NT_INLINE void kc_line_get(const KT& kt, uint32_t idx, uint32_t entry, ge_niels& q, uint32_t on) {
-  fe_0(q.ypx); fe_0(q.ymx); fe_0(q.xy2d);
-  if (on) kt.comb_load(idx, entry, q);
-}
-// p + q and p - q (completed -> p3)
-NT_HD NT_INLINE void kc_add_sub(ge_p3& sum, ge_p3& dif, const ge_p3& p, const ge_p3& q) {
-  ge_cached c;
-  ge_p3_to_cached(c, q);
-  ge_cp t;
-  ge_add_cached(t, p, c);
-  ge_cp_to_p3(sum, t);
-  ge_cached_cneg(c, 1u);
-  ge_add_cached(t, p, c);
-  ge_cp_to_p3(dif, t);
-}
-
-// ktab_build for a policy whose second pool holds combs: the claimers store the entry's header
-// and the 33 comb lines, and no window table.  Wave-uniform like ktab_build.
-//   * entry 32 = A (affine after decompression), then the 16 bases 2^(16 m) A, m = 4 t + j, off
-//     one chain of 240 doublings, parked as p3 points in entries 0..15 of the lane's table
-//     workspace `at` (idle after a fast or balanced row);
-//   * per block j: U+- = B[12+j] +- B[8+j], V+- = B[4+j] +- B[j] over the four bases' own
-//     workspace entries, then the eight U +- V: 12 additions.  Complete formulas: every entry is
-//     well defined for keys of small or mixed order (Z != 0; an entry may be the identity);
-//   * Montgomery's trick over all 32: entry n waits in its own comb line as (X c, Y c, Z) with
-//     c = Z_0 ... Z_(n-1), ONE inversion of the whole product, and the walk back turns line n
-//     into the affine niels entry with (X c)(c Z_n)^-1, (Y c)(c Z_n)^-1.  A lane reads back only
-//     lines it has stored itself; a lane that stores nothing computes on zeros.
-// All comb lines and the header are stored before drain_release(), then the slot word.
-template <class ATab, class KT>
-NT_HD NT_INLINE void ktab_build_comb(const uint32_t Aw[8], uint32_t claim, const KT& kt, ATab& at) {
-  static_assert(atab_entries_of<ATab>(0) >= kKcBases, "table workspace too small for the comb's bases");
-  const uint32_t fp = ktab_fp(Aw);
-  uint32_t idx = 0, have = 0;
-  if (claim != kKtNoSlot) {
-    idx = kt.pool_take();
-    have = idx < kt.capacity() ? 1u : 0u;
-    if (!have) kt.slot_store(claim, ktab_word(fp, kKtSeen));  // pool exhausted: seen for good
-  }
-  uint32_t flags, on;
-  {
-    ge_p3 P;
-    const uint32_t ok = ge_frombytes_w(P, Aw);
-    flags = (ok ? 0u : kKtUndecodable) | (ge_is_small_order_affine(P) ? kKtSmallOrder : 0u);
-    on = have & ok;
-    {
-      fe one;
-      fe_1(one);
-      ge_niels q;
-      ge_niels_from(q, P.X, P.Y, one);
-      kc_line_put(kt, idx, kKcSigned, q, on);
-    }
-#pragma unroll 1
-    for (uint32_t m = 0; m < kKcBases; ++m) {
-      kc_park_p3(at, m, P);
-      if (m + 1 < kKcBases) {
-        ge_p2 q;
-        ge_p3_to_p2(q, P);
-#pragma unroll 1
-        for (uint32_t r = 0; r + 1 < kKcCols; ++r) ge_dbl_p2(q, q);
-        ge_cp c;
-        ge_dbl(c, q);
-        ge_cp_to_p3(P, c);
-      }
-    }
-  }
-  fe c;  // Z_0 ... Z_(n-1)
-  fe_1(c);
-#pragma unroll 1
-  for (uint32_t j = 0; j < kKcBlocks; ++j) {
-#pragma unroll 1
-    for (uint32_t h = 0; h < 2; ++h) {  // h = 1: U+ -> 12 + j, U- -> 8 + j; h = 0: V+ -> 4 + j, V- -> j
-      ge_p3 a, b, s, d;
-      kc_take_p3(at, 8 * h + 4 + j, a);
-      kc_take_p3(at, 8 * h + j, b);
-      kc_add_sub(s, d, a, b);
-      kc_park_p3(at, 8 * h + 4 + j, s);
-      kc_park_p3(at, 8 * h + j, d);
-    }
-#pragma unroll 1
-    for (uint32_t e = 0; e < kKcPerBlock; ++e) {
-      // r2 = +1 (bit 2): U+, else U-.  (r1, r0) = ++: +V+, +-: +V-, -+: -V-, --: -V+
-      const uint32_t lo = e & 3u;
-      ge_p3 U, V;
-      kc_take_p3(at, (e & 4u ? 12u : 8u) + j, U);
-      kc_take_p3(at, (lo == 0u || lo == 3u ? 4u : 0u) + j, V);
-      ge_cached vc;
-      ge_p3_to_cached(vc, V);
-      ge_cached_cneg(vc, lo < 2u ? 1u : 0u);
-      ge_cp t;
-      ge_add_cached(t, U, vc);
-      ge_p2 r;
-      ge_cp_to_p2(r, t);
-      ge_niels w;
-      fe_mul(w.ypx, r.X, c);
-      fe_mul(w.ymx, r.Y, c);
-      w.xy2d = r.Z;
-      kc_line_put(kt, idx, kKcPerBlock * j + e, w, on);
-      fe_mul(c, c, r.Z);
-    }
-  }
-  fe inv;  // (Z_0 ... Z_n)^-1
-  fe_invert_batch(inv, c);
-#pragma unroll 1
-  for (int n = (int)kKcSigned - 1; n >= 0; --n) {
-    ge_niels w, q;
-    kc_line_get(kt, idx, (uint32_t)n, w, on);
-    ge_niels_from(q, w.ypx, w.ymx, inv);
-    fe_mul(inv, inv, w.xy2d);
-    kc_line_put(kt, idx, (uint32_t)n, q, on);
-  }
-  if (have) kt.hdr_store(idx, Aw, flags);
-  // every storing wave drains and releases before any slot word names its entry
-  kt.drain_release();
-  if (have) kt.slot_publish(claim, ktab_word(fp, kKtReady0 + idx));
-}
 // ktab_build of a row of verify_n: the comb where the policy carries one, the window tables otherwise
 template <class ATab, class KT>
 NT_HD NT_INLINE void ktab_build(const uint32_t Aw[8], uint32_t claim, const KT& kt, ATab& at) {
@@ -1171,300 +676,6 @@ NT_HD NT_INLINE void ktab_build(const uint32_t Aw[8], uint32_t claim, const KT& 
     }
   }
   ktab_build(Aw, claim, kt);
-}
-
-// t = -[u]A - [v]R (completed) from the key's three cached tables (pool entry
-// kidx; dead: the lane has no tables, its A digits are taken as zero) and the
-// lane's own table of -R: W windows, 4 (W - 1) doublings.  Window wi adds R's digit
-// wi and, of |u|'s 64 digits, digit wi of the first 16 on A, digit 16 + wi on A',
-// digit 32 + wi of the last 32 on A'' -- so any W <= 64 is right for any valid
-// vector, (k, 1) included.  The sign of u is folded into the digit.
-// The 16 digit words (v's at 0..7, |u|'s at 8..15) wait with kt.dig_put / dig_get (the kernel:
-// LDS) and a window reads the four it needs: held in registers through this loop they are the
-// first thing the allocator spills, and it then reloads them from scratch window by window.
-template <class KT>
-NT_HD NT_INLINE int32_t kt_digit(const KT& kt, uint32_t word0, int wi) {
-  return (int32_t)(((kt.dig_get(word0 + (uint32_t)(wi >> 3)) >> (4 * (wi & 7))) & 15u) ^ 8u) - 8;
-}
-template <class ATab, class KT>
-NT_HD NT_INLINE void ladder_a3r(ge_cp& t, uint32_t uneg, int W, const ATab& at, const KT& kt, uint32_t kidx) {
-#pragma unroll 1
-  for (int wi = W - 1; wi >= 0; --wi) {
-    int j = 0;
-    if (wi == W - 1) {
-      ge_cached ce;
-      at.load_signed(kTabR, kt_digit(kt, 0, wi), ce);
-      // cached -> completed with T = Z (as ladder_ar's seed)
-      fe_sub4(t.X, ce.YpX, ce.YmX);
-      fe_carry(t.X);
-      fe_add(t.Y, ce.YpX, ce.YmX);
-      fe_carry(t.Y);
-      t.Z = ce.Z2;
-      t.T = ce.Z2;
-      j = 1;
-    } else {
-      ge_p2 acc;
-      ge_cp_to_p2(acc, t);
-#pragma unroll 1
-      for (int r = 0; r < 3; ++r) ge_dbl_p2(acc, acc);
-      ge_dbl(t, acc);
-    }
-    // additions 0: R, 1: A'' (wi < 32), 2: A', 3: A (wi < 16).  The window's four digits are
-    // taken here and packed, so that the rolled loop below indexes nothing.
-    const int nj = wi < 16 ? 4 : (wi < 32 ? 2 : 1);
-    const int wl = wi & 15;
-    const uint32_t dpack = ((uint32_t)kt_digit(kt, 0, wi) & 15u) | (((uint32_t)kt_digit(kt, 12, wi & 31) & 15u) << 4) |
-                           (((uint32_t)kt_digit(kt, 10, wl) & 15u) << 8) | (((uint32_t)kt_digit(kt, 8, wl) & 15u) << 12);
-#pragma unroll 1
-    for (; j < nj; ++j) {
-      const int32_t d = (int32_t)(((dpack >> (4 * j)) & 15u) ^ 8u) - 8;  // sign-extended nibble
-      ge_cached ce;
-      if (j == 0) {
-        at.load_signed(kTabR, d, ce);
-      } else {
-        kt.tab_load_signed(kidx, 3u - (uint32_t)j, uneg ? d : -d, ce);  // -[u]A = [|u|](u < 0 ? A : -A)
-      }
-      ge_p3 q;
-      ge_cp_to_p3(q, t);
-      ge_add_cached(t, q, ce);
-    }
-  }
-}
-
-// verify_uv3's variable-base part, t = -[u]A - [v]R (completed): the digits of |u| and v
-// parked for ladder_a3r (dead: the key has no tables, its digits are zero), the window count
-// of the vector's bit lengths -- every lane of a wave runs its wave's largest -- and the ladder.
-// at holds the lane's table of -R already.
-template <class ATab, class KT>
-NT_HD NT_INLINE void ladder_uv3(ge_cp& t, const uint32_t u[8], uint32_t uneg, const uint32_t v[8], int ubits,
-                                int vbits, uint32_t dead, const ATab& at, const KT& kt, uint32_t kidx) {
-  uint32_t ud[8], vd[8];
-  sc_recode_w4(ud, u);
-  sc_recode_w4(vd, v);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    kt.dig_put((uint32_t)i, vd[i]);
-    kt.dig_put(8u + (uint32_t)i, dead ? 0u : ud[i]);
-  }
-  // 4 windows(b) >= b + 2: the signed top digit absorbs the carry
-  const int wv = (vbits + 5) >> 2, wu = ((ubits + 5) >> 2) - 32;
-  int Wn = wv > wu ? wv : wu;
-  Wn = Wn < 16 ? 16 : (Wn > 64 ? 64 : Wn);
-  const int W = wave_max(Wn);
-  ladder_a3r(t, uneg, W, at, kt, kidx);
-}
-
-// verify_uv for a key whose tables are cached: (u, v) any valid vector of k with
-// bit lengths <= ubits, vbits (verify_one uses sc_unbalanced's; the tests also run
-// the balanced one and (k, 1)); kflags = the entry's header flags.
-template <int MODE, class ATab, class WComb, class KT>
-NT_HD NT_INLINE uint32_t verify_uv3(const uint32_t Rw[8], const uint32_t Sw[8], const uint32_t u[8], uint32_t uneg,
-                                    const uint32_t v[8], int ubits, int vbits, uint32_t kflags, ATab& at,
-                                    const WComb& wb, const KT& kt, uint32_t kidx) {
-  const uint32_t dead = (kflags & kKtUndecodable) ? 1u : 0u;
-  uint32_t ok = sc_is_canonical(Sw) & (dead ^ 1u);
-  if (MODE == kStrict) ok &= (kflags & kKtSmallOrder) ? 0u : 1u;
-  {
-    ge_p3 R;
-    ok &= ge_frombytes_w(R, Rw);
-    if (MODE == kStrict) ok &= ge_is_small_order_affine(R) ^ 1u;
-    ptab_build(R, 1u, at, kTabR);
-  }
-  uint32_t w[8];
-  sc_mul(w, v, Sw);
-  ge_cp t;
-  ladder_uv3(t, u, uneg, v, ubits, vbits, dead, at, kt, kidx);
-  ge_p3 acc;
-  ge_cp_to_p3(acc, t);
-  wcomb_acc(acc, w, wb);
-  return ok & fe_iszero(acc.X) & fe_eq(acc.Y, acc.Z);
-}
-
-// t = [k](-A) (completed) for the full k < L from the key's FOUR cached tables (pool
-// entry kidx and its extension; dead: the key has no tables, its digits are taken as
-// zero): exactly 16 windows, 60 doublings, 64 additions, nothing of R and no lattice
-// vector.  k is recoded once into 64 signed nibbles; k < L < 2^253, so the top nibble is
-// at most 1 + carry and absorbs the carry (sc_recode_w4's bound, 2^255 - 2^251, is far
-// away).  Window wi adds digit wi on A, 16 + wi on A', 32 + wi on A'', 48 + wi on A''',
-// each with its sign flipped (the tables hold +A).  The 8 digit words wait with
-// kt.dig_put / dig_get as ladder_a3r's do.  The first window seeds the accumulator from
-// its first addition and doubles nothing.
-template <class KT>
-NT_HD NT_INLINE void ladder_k4(ge_cp& t, const uint32_t k[8], uint32_t dead, const KT& kt, uint32_t kidx) {
-  {
-    uint32_t kd[8];
-    sc_recode_w4(kd, k);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) kt.dig_put((uint32_t)i, dead ? 0u : kd[i]);
-  }
-#pragma unroll 1
-  for (int wi = 15; wi >= 0; --wi) {
-    // string s has its 16 digits in words 2s, 2s + 1: the window's four, packed, so that the
-    // rolled loop below indexes nothing
-    const uint32_t dpack = ((uint32_t)kt_digit(kt, 0, wi) & 15u) | (((uint32_t)kt_digit(kt, 2, wi) & 15u) << 4) |
-                           (((uint32_t)kt_digit(kt, 4, wi) & 15u) << 8) | (((uint32_t)kt_digit(kt, 6, wi) & 15u) << 12);
-    if (wi != 15) {
-      ge_p2 acc;
-      ge_cp_to_p2(acc, t);
-#pragma unroll 1
-      for (int r = 0; r < 3; ++r) ge_dbl_p2(acc, acc);
-      ge_dbl(t, acc);
-    }
-#pragma unroll 1
-    for (int j = 0; j < 4; ++j) {
-      const int32_t d = 8 - (int32_t)(((dpack >> (4 * j)) & 15u) ^ 8u);  // the nibble, sign-extended and negated
-      ge_cached ce;
-      if (j == 3) kt.ext_load_signed(kidx, d, ce);
-      else kt.tab_load_signed(kidx, (uint32_t)j, d, ce);
-      if (wi == 15 && j == 0) {
-        // cached -> completed with T = Z (as ladder_ar's seed)
-        fe_sub4(t.X, ce.YpX, ce.YmX);
-        fe_carry(t.X);
-        fe_add(t.Y, ce.YpX, ce.YmX);
-        fe_carry(t.Y);
-        t.Z = ce.Z2;
-        t.T = ce.Z2;
-      } else {
-        ge_p3 q;
-        ge_cp_to_p3(q, t);
-        ge_add_cached(t, q, ce);
-      }
-    }
-  }
-}
-
-// The check for a key whose four tables are cached (kflags = the entry's header flags),
-// k = the full hash scalar:
-//   ok  <=>  s < L, A decodes, (strict) A is not of small order, and R' = [s]B - [k]A
-//            encodes to R's bytes the way dalek compares points (enc_matches), (strict)
-//            R' not of small order
-// -- verify_uv's verdict for every input: with v odd and below L, [v]([s]B - [k]A - R) is
-// the identity only if R decodes to R' itself.  R is never decompressed, the lane's table
-// workspace is not touched, and s goes to the comb as it is.
-template <int MODE, class WComb, class KT>
-NT_HD NT_INLINE uint32_t verify_k4(const uint32_t Rw[8], const uint32_t Sw[8], const uint32_t k[8], uint32_t kflags,
-                                   const WComb& wb, const KT& kt, uint32_t kidx) {
-  const uint32_t dead = (kflags & kKtUndecodable) ? 1u : 0u;
-  uint32_t ok = sc_is_canonical(Sw) & (dead ^ 1u);
-  if (MODE == kStrict) ok &= (kflags & kKtSmallOrder) ? 0u : 1u;
-  ge_cp t;
-  ladder_k4(t, k, dead, kt, kidx);
-  ge_p3 acc;
-  ge_cp_to_p3(acc, t);
-  wcomb_acc(acc, Sw, wb);
-  fe zi;
-  fe_invert_batch(zi, acc.Z);
-  ge_p2 P;
-  ge_p3_to_p2(P, acc);
-  return ok & compare_one<MODE>(P, zi, Rw, MODE == kStrict);
-}
-
-// The comb lookup of column col, block j (both wave-uniform): bit 16 j + col of each limb
-// W_t (words 2 t, 2 t + 1 of the parked W), the top tooth's sign factored out.  Returns
-// entry | negate << 8: the tables hold +A and the ladder sums -[K]A, so the entry is negated
-// where the top tooth's bit is set.
-template <class KT>
-NT_HD NT_INLINE uint32_t kc_pick(const KT& kt, uint32_t col, uint32_t j) {
-  const uint32_t w = j >> 1, sh = 16u * (j & 1u) + col;
-  const uint32_t b3 = (kt.dig_get(6u + w) >> sh) & 1u;
-  uint32_t e = 0;
-#pragma unroll
-  for (uint32_t t = 0; t < kKcTeeth - 1; ++t) e |= ((((kt.dig_get(2u * t + w) >> sh) & 1u) ^ b3) ^ 1u) << t;
-  return (kKcPerBlock * j + e) | (b3 << 8);
-}
-// comb line `entry` of the key's entry kidx; off: the identity instead (the load still goes to
-// an in-range line and is dropped)
-template <class KT>
-NT_HD NT_INLINE void kc_load(ge_niels& ne, const KT& kt, uint32_t kidx, uint32_t entry, uint32_t off) {
-  kt.comb_load(kidx, entry, ne);
-  ge_niels z;
-  ge_niels_0(z);
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    ne.ypx.v[i] = off ? z.ypx.v[i] : ne.ypx.v[i];
-    ne.ymx.v[i] = off ? z.ymx.v[i] : ne.ymx.v[i];
-    ne.xy2d.v[i] = off ? z.xy2d.v[i] : ne.xy2d.v[i];
-  }
-}
-
-// The comb's recoding of the full hash scalar k < L: K = k | 1, W = (K >> 1) | 2^255 (k < 2^253:
-// bit 255 is free).  The 8 words of W wait with kt.dig_put / dig_get as ladder_k4's digits do
-// (the kernel: LDS), word 8 holds c = 1 - (k & 1).
-template <class KT>
-NT_HD NT_INLINE void kc_recode(const uint32_t k[8], const KT& kt) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint32_t lo = i == 0 ? (k[0] | 1u) : k[i];
-    kt.dig_put((uint32_t)i, (lo >> 1) | (i < 7 ? k[i + 1] << 31 : 0x80000000u));
-  }
-  kt.dig_put(8u, (k[0] & 1u) ^ 1u);
-}
-// t = [k](-A) (completed) for the full k < L from the key's comb (pool entry kidx's lines of
-// the second pool; dead: the key has no comb, every lookup is the identity): 64 lookups, 15
-// doublings, 64 mixed additions and the parity's correction, nothing of R and no lattice vector.
-// Columns 15 .. 0, one doubling before each but the first (from the completed point:
-// ge_cp_to_p2 + ge_dbl), blocks 0 .. 3 within a column; the first lookup seeds the accumulator;
-// the last addition, executed by every lane, is +A where c = 1 (-[K]A + A = -[k]A) and the
-// identity where c = 0.  The next entry's load is issued right after the multiplies that consume
-// the current one, one ahead and no further, as in wcomb_acc.  Column and block are wave-uniform:
-// nothing is indexed per lane.
-template <class KT>
-NT_HD NT_INLINE void ladder_kc(ge_cp& t, const uint32_t k[8], uint32_t dead, const KT& kt, uint32_t kidx) {
-  kc_recode(k, kt);
-  constexpr uint32_t kTop = kKcCols - 1;
-  uint32_t pk = kc_pick(kt, kTop, 0u);
-  ge_niels ne;
-  kc_load(ne, kt, kidx, pk & 0xffu, dead);
-  ge_niels_cneg(ne, pk >> 8);
-  ge_p3 acc;
-  ge_p3_from_niels(acc, ne);
-  pk = kc_pick(kt, kTop, 1u);
-  kc_load(ne, kt, kidx, pk & 0xffu, dead);
-#pragma unroll 1
-  for (uint32_t col = kTop + 1; col-- > 0;) {
-    if (col != kTop) {
-      ge_p2 q;
-      ge_cp_to_p2(q, t);
-      ge_dbl(t, q);
-    }
-#pragma unroll 1
-    for (uint32_t j = col == kTop ? 1u : 0u; j < kKcBlocks; ++j) {
-      if (col != kTop || j != 1u) ge_cp_to_p3(acc, t);
-      ge_niels_cneg(ne, pk >> 8);
-      fe PP, MM, TT;
-      ge_add_niels_1(PP, MM, TT, acc, ne);
-      if (j + 1 < kKcBlocks || col != 0) {
-        pk = j + 1 < kKcBlocks ? kc_pick(kt, col, j + 1) : kc_pick(kt, col - 1, 0u);
-        kc_load(ne, kt, kidx, pk & 0xffu, dead);
-      } else {
-        // the correction: +A, never negated
-        kc_load(ne, kt, kidx, kKcSigned, dead | (kt.dig_get(8u) ^ 1u));
-      }
-      ge_add_niels_2(t, PP, MM, TT, acc.Z);
-    }
-  }
-  ge_cp_to_p3(acc, t);
-  ge_add_niels(t, acc, ne);
-}
-
-// verify_k4 over the key's comb instead of its four tables: the same verdict for every input
-// (ladder_kc's sum is [k](-A) as an integer identity), everything after the ladder unchanged.
-template <int MODE, class WComb, class KT>
-NT_HD NT_INLINE uint32_t verify_kc(const uint32_t Rw[8], const uint32_t Sw[8], const uint32_t k[8], uint32_t kflags,
-                                   const WComb& wb, const KT& kt, uint32_t kidx) {
-  const uint32_t dead = (kflags & kKtUndecodable) ? 1u : 0u;
-  uint32_t ok = sc_is_canonical(Sw) & (dead ^ 1u);
-  if (MODE == kStrict) ok &= (kflags & kKtSmallOrder) ? 0u : 1u;
-  ge_cp t;
-  ladder_kc(t, k, dead, kt, kidx);
-  ge_p3 acc;
-  ge_cp_to_p3(acc, t);
-  wcomb_acc(acc, Sw, wb);
-  fe zi;
-  fe_invert_batch(zi, acc.Z);
-  ge_p2 P;
-  ge_p3_to_p2(P, acc);
-  return ok & compare_one<MODE>(P, zi, Rw, MODE == kStrict);
 }
 
 // One verification (A, R, s encodings as words), half-size scalars:
@@ -1618,11 +829,7 @@ NT_HD NT_INLINE uint32_t cached_point(ge_p3& acc, uint32_t meta, const uint32_t 
   if (is_strict<MODE>(meta)) okj &= (meta & kKeySmallOrder) ? 0u : 1u;
   uint32_t k[8];
   hram_scalar<true>(k, Rw, Aw, msg, len);
-#ifdef NT_EXPERIMENT_KEY_SKIP
-  wcomb_acc<WCombA, true, NT_EXPERIMENT_KEY_SKIP>(acc, k, ca);  // timing only: wrong verdicts
-#else
   key_comb_sum(acc, k, meta, ca);
-#endif
   wcomb_acc(acc, Sw, cb);
   return okj;
 }

@@ -34,17 +34,10 @@ namespace nt { extern unsigned long long g_fe_mul, g_fe_sq; }
 // Scheduling fence after each multiply: the 10 column chains inside one mul
 // are enough ILP for a wave; letting the scheduler overlap several muls only
 // multiplies register pressure (spills, lower occupancy).
-// -DNT_FENCE_POINT (A/B builds): fence after each point operation instead, so
-// the 3-4 independent multiplies of one formula may interleave.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(NT_NO_MUL_FENCE) && !defined(NT_FENCE_POINT)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(NT_NO_MUL_FENCE)
 #define NT_MUL_FENCE() __builtin_amdgcn_sched_barrier(0)
 #else
 #define NT_MUL_FENCE() ((void)0)
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && defined(NT_FENCE_POINT)
-#define NT_POINT_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define NT_POINT_FENCE() ((void)0)
 #endif
 
 // Pins a value as a 32-bit VGPR (no instruction emitted).  Without it LLVM
@@ -96,13 +89,6 @@ NT_HD NT_INLINE void fe_sub4(fe& h, const fe& f, const fe& g) {
   h.v[0] = f.v[0] + 0xfffffb4u - g.v[0];
 #pragma unroll
   for (int i = 1; i < 10; ++i) h.v[i] = f.v[i] + ((i & 1) ? 0x7fffffcu : 0xffffffcu) - g.v[i];
-}
-
-// h = 2f + 4p - g   (f reduced, g as fe_sub4): one shift-add and one subtract per limb
-NT_HD NT_INLINE void fe_dbl_sub4(fe& h, const fe& f, const fe& g) {
-  h.v[0] = (f.v[0] << 1) + (0xfffffb4u - g.v[0]);
-#pragma unroll
-  for (int i = 1; i < 10; ++i) h.v[i] = (f.v[i] << 1) + (((i & 1) ? 0x7fffffcu : 0xffffffcu) - g.v[i]);
 }
 
 // h = 2p - f  (f reduced)

@@ -37,14 +37,12 @@ NT_HD NT_INLINE void ge_cp_to_p2(ge_p2& r, const ge_cp& p) {
   fe_mul(r.X, p.T, p.X);
   fe_mul(r.Y, p.Y, p.Z);
   fe_mul(r.Z, p.T, p.Z);
-  NT_POINT_FENCE();
 }
 NT_HD NT_INLINE void ge_cp_to_p3(ge_p3& r, const ge_cp& p) {
   fe_mul(r.X, p.T, p.X);
   fe_mul(r.Y, p.Y, p.Z);
   fe_mul(r.Z, p.T, p.Z);
   fe_mul(r.T, p.Y, p.X);
-  NT_POINT_FENCE();
 }
 NT_HD NT_INLINE void ge_p3_to_p2(ge_p2& r, const ge_p3& p) { r.X = p.X; r.Y = p.Y; r.Z = p.Z; }
 
@@ -53,22 +51,13 @@ NT_HD NT_INLINE void ge_p3_to_p2(ge_p2& r, const ge_p3& p) { r.X = p.X; r.Y = p.
 // from "R" coordinates Y + X < 2^27 (even) / 2^26.01 (odd), Y + 2p - X < 2^27.58,
 // 2Z < 2^27 -- all within fe_mul's g bound 2^27.75.  (The ladder's seed, which
 // subtracts two of them, uses fe_sub4.)
-#ifndef NT_CACHED_NOCARRY
-#define NT_CACHED_NOCARRY 1
-#endif
 NT_HD NT_INLINE void ge_p3_to_cached(ge_cached& r, const ge_p3& p) {
   fe d2;
   fe_const(d2, kFeD2);
   fe_add(r.YpX, p.Y, p.X);
   fe_sub(r.YmX, p.Y, p.X);
   fe_add(r.Z2, p.Z, p.Z);
-#if !NT_CACHED_NOCARRY
-  fe_carry(r.YpX);
-  fe_carry(r.YmX);
-  fe_carry(r.Z2);
-#endif
   fe_mul(r.T2d, p.T, d2);
-  NT_POINT_FENCE();
 }
 
 // 2P from a p2 point with "R" coordinates (dalek ProjectivePoint::double).
@@ -83,16 +72,8 @@ NT_HD NT_INLINE void ge_dbl(ge_cp& r, const ge_p2& p) {
   fe_sub(r.Z, YY, XX);        // Z' = YY - XX (2p)      < 2^27.6
   fe_sub4(r.X, S, r.Y);       // X' = S - Y'  (4p)      < 2^28.6 -> carry
   fe_carry(r.X);
-#ifndef NT_DBL_SUB4
-#define NT_DBL_SUB4 0
-#endif
-#if NT_DBL_SUB4
-  fe_dbl_sub4(r.T, ZZ, r.Z);  // T' = 2ZZ - Z' (4p)     < 2^28.6 (f-side only)
-#else
   fe_add(ZZ, ZZ, ZZ);
-  fe_sub4(r.T, ZZ, r.Z);
-#endif
-  NT_POINT_FENCE();
+  fe_sub4(r.T, ZZ, r.Z);      // T' = 2ZZ - Z' (4p)     < 2^28.6 (f-side only)
 }
 
 // P + Q (neg=0) or P - Q (neg=1), Q cached with "R" coordinates.
@@ -108,7 +89,6 @@ NT_HD NT_INLINE void ge_add_cached(ge_cp& r, const ge_p3& p, const ge_cached& q)
   fe_add(r.Y, PP, MM);
   fe_add(r.Z, ZZ, TT);
   fe_sub(r.T, ZZ, TT);
-  NT_POINT_FENCE();
 }
 
 // P + Q, Q affine niels.  Split in two halves so a caller can issue its next
@@ -120,7 +100,6 @@ NT_HD NT_INLINE void ge_add_niels_1(fe& PP, fe& MM, fe& TT, const ge_p3& p, cons
   fe_mul(PP, a, q.ypx);
   fe_mul(MM, b, q.ymx);
   fe_mul(TT, p.T, q.xy2d);
-  NT_POINT_FENCE();
 }
 NT_HD NT_INLINE void ge_add_niels_2(ge_cp& r, const fe& PP, const fe& MM, const fe& TT, const fe& Z) {
   fe ZZ;
@@ -129,7 +108,6 @@ NT_HD NT_INLINE void ge_add_niels_2(ge_cp& r, const fe& PP, const fe& MM, const 
   fe_add(r.Y, PP, MM);
   fe_add(r.Z, ZZ, TT);
   fe_sub(r.T, ZZ, TT);        // ZZ + 2p - TT < 2^27.6
-  NT_POINT_FENCE();
 }
 NT_HD NT_INLINE void ge_add_niels(ge_cp& r, const ge_p3& p, const ge_niels& q) {
   fe PP, MM, TT;
@@ -150,7 +128,6 @@ NT_HD NT_INLINE void ge_p3_from_niels(ge_p3& r, const ge_niels& q) {
   fe_0(r.Z);
   r.Z.v[0] = 2;
   fe_mul(r.T, q.xy2d, dinv);  // xy2d: niels (< 2^26) or its fe_neg (f side)
-  NT_POINT_FENCE();
 }
 
 // Affine niels entry of the projective point (X:Y:Z), given zi = Z^-1.
@@ -165,7 +142,6 @@ NT_HD NT_INLINE void ge_niels_from(ge_niels& q, const fe& X, const fe& Y, const 
   fe_const(d2, kFeD2);
   fe_mul(q.xy2d, x, y);
   fe_mul(q.xy2d, q.xy2d, d2);
-  NT_POINT_FENCE();
 }
 
 // Conditionally negate a cached entry in place: -(Y+X, Y-X, 2Z, 2dT) = (Y-X, Y+X, 2Z, -2dT)

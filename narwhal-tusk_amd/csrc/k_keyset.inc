@@ -112,63 +112,6 @@ __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify_keyset(
 // stash; when the counter passes `rows` (or the stash is full) it inverts once
 // and finishes its rows backwards, reading their row indices from LDS.  Same
 // per-signature arithmetic as verify_cached_batch (ed25519_ops.hpp).
-//
-// NT_KS_WG_INV: the LAST batch of every wave (the one that ends because the
-// counter ran out) shares ONE inversion with the other three waves of its
-// workgroup: the waves leave their per-lane Z products in LDS, one wave (rotated
-// over the blocks) inverts their product and hands each wave its inverse back (Montgomery's trick over
-// the four waves, 9 multiplies), so a launch pays one inversion per workgroup
-// instead of one per wave.  Every wave of the block -- surplus waves beyond
-// `waves` included, with no rows and a product of 1 -- reaches that step
-// exactly once (its loop ends with it), so both barriers are met by all 256
-// threads.  Batches that end because a wave's stash is full still invert
-// privately.
-#ifndef NT_KS_WG_INV
-#define NT_KS_WG_INV 0
-#endif
-
-// inv = acc^-1 for this wave's lanes, via one inversion shared by the block's
-// kBlock / 64 waves (Montgomery's trick in LDS; every thread of the block calls
-// it).  Wave `who` inverts: blocks rotate it, so the blocks sharing a CU put
-// their inversions on different SIMDs.
-NT_D NT_INLINE void ks_block_invert(fe& inv, const fe& acc, uint32_t wib, uint32_t lane,
-                                    uint32_t (*s_acc)[10][64], uint32_t who) {
-  constexpr int kW = kBlock / 64;
-  static_assert(kW == 4, "the product tree below is written for four waves per block");
-#pragma unroll
-  for (int i = 0; i < 10; ++i) s_acc[wib][i][lane] = acc.v[i];
-  __syncthreads();
-  if (wib == who) {
-    fe a[kW];
-#pragma unroll
-    for (int w = 0; w < kW; ++w)
-#pragma unroll
-      for (int i = 0; i < 10; ++i) a[w].v[i] = s_acc[w][i][lane];
-    fe p1, p2, p3, t, o;
-    fe_mul(p1, a[0], a[1]);
-    fe_mul(p2, p1, a[2]);
-    fe_mul(p3, p2, a[3]);
-    fe_invert_batch(t, p3);  // 1 / (a0 a1 a2 a3)
-    fe_mul(o, t, p2);        // 1 / a3
-#pragma unroll
-    for (int i = 0; i < 10; ++i) s_acc[3][i][lane] = o.v[i];
-    fe_mul(t, t, a[3]);      // 1 / (a0 a1 a2)
-    fe_mul(o, t, p1);        // 1 / a2
-#pragma unroll
-    for (int i = 0; i < 10; ++i) s_acc[2][i][lane] = o.v[i];
-    fe_mul(t, t, a[2]);      // 1 / (a0 a1)
-    fe_mul(o, t, a[0]);      // 1 / a1
-#pragma unroll
-    for (int i = 0; i < 10; ++i) s_acc[1][i][lane] = o.v[i];
-    fe_mul(o, t, a[1]);      // 1 / a0
-#pragma unroll
-    for (int i = 0; i < 10; ++i) s_acc[0][i][lane] = o.v[i];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 10; ++i) inv.v[i] = s_acc[wib][i][lane];
-}
-
 template <int MODE, int OCC, int WA, int WB>
 __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify_keyset_stream(
     const uint32_t* __restrict__ key_idx, const uint32_t* __restrict__ sig, const uint8_t* __restrict__ msg,
@@ -182,18 +125,11 @@ __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify_keyset_stream(
   __shared__ uint32_t s_rows[kBlock / 64][kKsPerLane];
   const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
   const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-#if NT_KS_WG_INV
-  __shared__ uint32_t s_acc[kBlock / 64][10][64];
-  // the last block's surplus waves (no stash region) take no rows but join the shared inversion
-  const bool live = wave < waves;
-#else
   if (wave >= waves) return;  // the last block's surplus waves (no stash region)
-  const bool live = true;
-#endif
-  const KsStash st{stash + (size_t)(live ? wave : 0) * prow * kKsQuads * 64};
+  const KsStash st{stash + (size_t)wave * prow * kKsQuads * 64};
   uint32_t claim = 0;
-  if (live && lane == 0) claim = atomicAdd(row_ctr, 1u);
-  uint32_t r = live ? __builtin_amdgcn_readfirstlane(claim) : rows;
+  if (lane == 0) claim = atomicAdd(row_ctr, 1u);
+  uint32_t r = __builtin_amdgcn_readfirstlane(claim);
 #pragma unroll 1
   for (;;) {
     uint64_t okbits = 0, strictbits = 0;
@@ -223,13 +159,8 @@ __global__ __launch_bounds__(kBlock, OCC) void k_ed25519_verify_keyset_stream(
     }
     const bool last = r >= rows;  // wave-uniform: the counter ran out (else the stash is full)
     fe inv;
-#if NT_KS_WG_INV
-    if (last) ks_block_invert(inv, acc, wib, lane, s_acc, blockIdx.x % (kBlock / 64));
-    else fe_invert_batch(inv, acc);
-#else
     if (m == 0) break;
     fe_invert_batch(inv, acc);
-#endif
 #pragma unroll 1
     for (int j = m - 1; j >= 0; --j) {
       ge_p2 P;

@@ -34,7 +34,7 @@ inline uint32_t xcache_slots_pow2(unsigned long long want, uint32_t cap) {
   while (s < cap && 2ull * s <= want) s <<= 1;
   return s;
 }
-// The key-table cache of a verify launch (kernels_common.hpp DevKTab; ed25519_ops.hpp KTab):
+// The key-table cache of a verify launch (kernels_common.hpp DevKTab; ktab.hpp):
 // base = the control block (kKTabCtlBytes: words 0..3 = entries handed out, fast-path rows, builds,
 // old-path rows; words 4..5 = the pool's device address, 128-byte aligned entries of
 // ktab_entry_bytes(); word 6 = index slots - 1, a power of two of whole buckets; words 8..9 = the

@@ -34,172 +34,101 @@ NT_D NT_INLINE void aux_priority() {
 // signatures per lane per block iteration of k_ed25519_verify (1 or 2; A/B builds)
 constexpr int kVPer = NT_VERIFY_PER_LANE;
 constexpr int kAEntries = 18;         // j*(+-A) and j*(-R), |digit| in 0..8
-// Signed entries (NT_ATAB_SIGNED=1): each cached coordinate in its own 3-quad
-// slot -- Y+X, Y-X, 2Z, 2dT and -2dT -- so a lookup of digit -j reads the slots
-// of +j in swapped order (per-lane addresses) instead of negating the entry
-// with 10 subtracts and 30 selects (ge_cached_cneg) on every ladder addition.
-#ifndef NT_ATAB_SIGNED
-#define NT_ATAB_SIGNED 0
-#endif
-constexpr int kAQuads = NT_ATAB_SIGNED ? 15 : 10;  // uint4 per entry
+constexpr int kAQuads = 10;           // uint4 per entry
 
 // --------------------------------------------------------------------------
 // Table accessors
 // --------------------------------------------------------------------------
+// N uint4 <-> 4 N words.  Quad i lies at p[i], or where the layout's own index expression
+// at(i) says (KsStash: a fixed stride from quad 0 instead compiles to other addressing and
+// another register allocation of the key-cache kernels).
+template <int N, class At>
+NT_D NT_INLINE void ld_quads_at(uint32_t* w, const At& at) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const uint4 v = *at(i);
+    w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+  }
+}
+template <int N, class At>
+NT_D NT_INLINE void st_quads_at(const At& at, const uint32_t* w) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) *at(i) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+}
+template <int N>
+NT_D NT_INLINE void ld_quads(uint32_t* w, const uint4* p) {
+  ld_quads_at<N>(w, [p](int i) { return p + i; });
+}
+template <int N>
+NT_D NT_INLINE void st_quads(uint4* p, const uint32_t* w) {
+  st_quads_at<N>([p](int i) { return p + i; }, w);
+}
+// 30 words <-> an affine niels entry, 40 words <-> a cached point
+NT_D NT_INLINE void niels_of_words(ge_niels& q, const uint32_t* w) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) { q.ypx.v[i] = w[i]; q.ymx.v[i] = w[10 + i]; q.xy2d.v[i] = w[20 + i]; }
+}
+NT_D NT_INLINE void words_of_niels(uint32_t* w, const ge_niels& q) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) { w[i] = q.ypx.v[i]; w[10 + i] = q.ymx.v[i]; w[20 + i] = q.xy2d.v[i]; }
+}
+NT_D NT_INLINE void cached_of_words(ge_cached& c, const uint32_t* w) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) { c.YpX.v[i] = w[i]; c.YmX.v[i] = w[10 + i]; c.Z2.v[i] = w[20 + i]; c.T2d.v[i] = w[30 + i]; }
+}
+NT_D NT_INLINE void words_of_cached(uint32_t* w, const ge_cached& c) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) { w[i] = c.YpX.v[i]; w[10 + i] = c.YmX.v[i]; w[20 + i] = c.Z2.v[i]; w[30 + i] = c.T2d.v[i]; }
+}
+
 // Wide comb of one point with digit width W, layout [pos][entry][32 words];
 // 8 x 16-byte loads.
-#ifndef NT_COMB_NT
-#define NT_COMB_NT 0
-#endif
 template <int W>
 struct WideComb {
   static constexpr int kBits = W;
   const uint32_t* base;
   NT_D NT_INLINE void load(uint32_t pos, uint32_t idx, ge_niels& q) const {
-#ifdef NT_EXPERIMENT_CACHED_COMB
-    idx &= 7;  // timing experiment only (wrong results): every lookup hits in cache
-#endif
-#ifdef NT_EXPERIMENT_BHALF
-    if (W == kBCombBits) idx >>= 1;  // timing experiment only (wrong results): half of each position's table
-#endif
-#ifdef NT_EXPERIMENT_KHALF
-    if (W == kKeyCombWide) idx >>= 1;  // timing experiment only (wrong results): half of each key position's table
-#endif
-    const uint4* e = (const uint4*)(base + ((size_t)pos * CombGeom<W>::kEntries + idx) * kWStride);
     uint32_t w[32];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#if NT_COMB_NT
-      // A/B build (-DNT_COMB_NT=1): non-temporal loads -- a random comb line is read once
-      typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-      const u4v t = __builtin_nontemporal_load((const u4v*)e + i);
-      const uint4 v = make_uint4(t.x, t.y, t.z, t.w);
-#else
-      const uint4 v = e[i];
-#endif
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      q.ypx.v[i] = w[i];
-      q.ymx.v[i] = w[10 + i];
-      q.xy2d.v[i] = w[20 + i];
-    }
+    ld_quads<8>(w, (const uint4*)(base + ((size_t)pos * CombGeom<W>::kEntries + idx) * kWStride));
+    niels_of_words(q, w);
   }
   // the point's [L]P entry after the positions (reduced-scalar combs, CombGeom::kCorrWord)
   NT_D NT_INLINE void load_corr(ge_niels& q) const {
-    const uint4* e = (const uint4*)(base + CombGeom<W>::kCorrWord);
     uint32_t w[32];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const uint4 v = e[i];
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      q.ypx.v[i] = w[i];
-      q.ymx.v[i] = w[10 + i];
-      q.xy2d.v[i] = w[20 + i];
-    }
+    ld_quads<8>(w, (const uint4*)(base + CombGeom<W>::kCorrWord));
+    niels_of_words(q, w);
   }
 };
 
-// Per-lane point tables in the global workspace, uint4 granules.  Lane-major
-// ([slot][lane][entry][quad], NT_ATAB_LANE_MAJOR=1): an entry is 160 contiguous
-// bytes of one lane, so the 10 loads of a table lookup use every byte of the
-// ~1.5 lines they fetch.  Lane-minor ([slot][entry][quad][lane]): a lookup's
-// loads coalesce only among lanes that picked the same entry -- with 9 entry
+// Per-lane point tables in the global workspace, uint4 granules, lane-major
+// ([slot][lane][entry][quad]): an entry is 160 contiguous bytes of one lane, so
+// the 10 loads of a table lookup use every byte of the ~1.5 lines they fetch.
+// Why not lane-minor ([slot][entry][quad][lane]): a lookup's loads would
+// coalesce only among lanes that picked the same entry -- with 9 entry
 // magnitudes per 8-lane line that fetched ~5x the bytes used (PMC v7: 63 GB per
 // 1M-verify launch, 5.5 TB/s).  Measured (same box, interleaved): lane-major
 // 95.5 vs lane-minor 88.1 M verifies/s.
-#ifndef NT_ATAB_LANE_MAJOR
-#define NT_ATAB_LANE_MAJOR 1
-#endif
 struct WsATab {
   uint4* ws;
   uint32_t slot;
   static constexpr uint32_t kEntries = kAEntries;  // what ktab_build_comb checks its 16 bases against
-#if NT_ATAB_LANE_MAJOR
-  static constexpr size_t kQuadStride = 1;
   NT_D NT_INLINE uint4* at(uint32_t entry) const {
     return ws + ((size_t)(slot * kBlock + threadIdx.x) * kAEntries + entry) * kAQuads;
   }
-#else
-  static constexpr size_t kQuadStride = kBlock;
-  NT_D NT_INLINE uint4* at(uint32_t entry) const {
-    return ws + ((size_t)(slot * kAEntries + entry) * kAQuads) * kBlock + threadIdx.x;
-  }
-#endif
-#if NT_ATAB_SIGNED
-  // slot k of an entry: 3 quads, words 0..9 used
-  NT_D NT_INLINE void store_fe(uint4* q, const fe& f) const {
-    q[0 * kQuadStride] = make_uint4(f.v[0], f.v[1], f.v[2], f.v[3]);
-    q[1 * kQuadStride] = make_uint4(f.v[4], f.v[5], f.v[6], f.v[7]);
-    q[2 * kQuadStride] = make_uint4(f.v[8], f.v[9], 0u, 0u);
-  }
-  NT_D NT_INLINE void load_fe(const uint4* q, fe& f) const {
-    const uint4 a = q[0 * kQuadStride], b = q[1 * kQuadStride], c = q[2 * kQuadStride];
-    f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-    f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-    f.v[8] = c.x; f.v[9] = c.y;
-  }
-  NT_D NT_INLINE void store(uint32_t entry, const ge_cached& c) const {
-    uint4* base = at(entry);
-    fe n;
-    fe_neg(n, c.T2d);  // T2d is a multiply output (reduced): 2p - T2d < 2^27
-    store_fe(base, c.YpX);
-    store_fe(base + 3 * kQuadStride, c.YmX);
-    store_fe(base + 6 * kQuadStride, c.Z2);
-    store_fe(base + 9 * kQuadStride, c.T2d);
-    store_fe(base + 12 * kQuadStride, n);
-  }
-  // entry e0 + |d| negated when d < 0: -(Y+X, Y-X, 2Z, 2dT) = (Y-X, Y+X, 2Z, -2dT)
-  NT_D NT_INLINE void load_signed(uint32_t e0, int32_t d, ge_cached& c) const {
-    const uint32_t neg = d < 0 ? 1u : 0u;
-    uint32_t entry = e0 + (uint32_t)(d < 0 ? -d : d);
-#ifdef NT_EXPERIMENT_CACHED_ATAB
-    entry = entry >= kTabR ? kTabR + 1 : 1;  // timing experiment only (wrong results): lookups hit one entry
-#endif
-    const uint4* base = at(entry);
-    load_fe(base + (neg ? 3 : 0) * kQuadStride, c.YpX);
-    load_fe(base + (neg ? 0 : 3) * kQuadStride, c.YmX);
-    load_fe(base + 6 * kQuadStride, c.Z2);
-    load_fe(base + (neg ? 12 : 9) * kQuadStride, c.T2d);
-  }
-  NT_D NT_INLINE void load(uint32_t entry, ge_cached& c) const { load_signed(entry, 0, c); }
-#else
   NT_D NT_INLINE void load_signed(uint32_t e0, int32_t d, ge_cached& c) const {
     load(e0 + (uint32_t)(d < 0 ? -d : d), c);
     ge_cached_cneg(c, d < 0);
   }
   NT_D NT_INLINE void store(uint32_t entry, const ge_cached& c) const {
     uint32_t w[40];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      w[i] = c.YpX.v[i]; w[10 + i] = c.YmX.v[i]; w[20 + i] = c.Z2.v[i]; w[30 + i] = c.T2d.v[i];
-    }
-    uint4* base = at(entry);
-#pragma unroll
-    for (int q = 0; q < kAQuads; ++q)
-      base[q * kQuadStride] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+    words_of_cached(w, c);
+    st_quads<kAQuads>(at(entry), w);
   }
   NT_D NT_INLINE void load(uint32_t entry, ge_cached& c) const {
-#ifdef NT_EXPERIMENT_CACHED_ATAB
-    entry = entry >= kTabR ? kTabR + 1 : 1;  // timing experiment only (wrong results): lookups hit one entry
-#endif
     uint32_t w[40];
-    const uint4* base = at(entry);
-#pragma unroll
-    for (int q = 0; q < kAQuads; ++q) {
-      const uint4 v = base[q * kQuadStride];
-      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      c.YpX.v[i] = w[i]; c.YmX.v[i] = w[10 + i]; c.Z2.v[i] = w[20 + i]; c.T2d.v[i] = w[30 + i];
-    }
+    ld_quads<kAQuads>(w, at(entry));
+    cached_of_words(c, w);
   }
-#endif
 };
 
 // The x cache of the verify kernel (ed25519_ops.hpp XCache): `msk + 1` slots of
@@ -226,7 +155,7 @@ struct DevXCache {
   }
 };
 
-// The key-table cache of the verify kernel (ed25519_ops.hpp KTab) in global memory, one per
+// The key-table cache of the verify kernel (ktab.hpp) in global memory, one per
 // device entry, read and written by launches on any stream with no ordering between them.
 // Shared words (index slots, control block) are only ever touched by agent-scope atomics; pool
 // entries by plain VECTOR accesses (per-lane addresses through a non-restrict pointer: never the
@@ -348,37 +277,26 @@ struct DevKTab {
   }
   NT_D NT_INLINE void comb_store(uint32_t idx, uint32_t entry, const ge_niels& q) const {
     uint32_t w[30];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) { w[i] = q.ypx.v[i]; w[10 + i] = q.ymx.v[i]; w[20 + i] = q.xy2d.v[i]; }
+    words_of_niels(w, q);
     uint4* p = comb_line(idx, entry);
-#pragma unroll
-    for (int i = 0; i < 7; ++i) p[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    st_quads<7>(p, w);
     *(uint2*)(p + 7) = make_uint2(w[28], w[29]);
   }
   NT_D NT_INLINE void comb_load(uint32_t idx, uint32_t entry, ge_niels& q) const {
     uint32_t w[30];
     const uint4* p = comb_line(idx, entry);
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const uint4 v = p[i];
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
+    ld_quads<7>(w, p);
     const uint2 h = *(const uint2*)(p + 7);
     w[28] = h.x; w[29] = h.y;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) { q.ypx.v[i] = w[i]; q.ymx.v[i] = w[10 + i]; q.xy2d.v[i] = w[20 + i]; }
+    niels_of_words(q, w);
   }
   NT_D NT_INLINE uint4* ext_point(uint32_t idx, uint32_t j) const {
     return ext_ptr() + (size_t)idx * kExtQuads + ((j - 1u) & (kKtPerTable - 1u)) * 10u;
   }
   NT_D NT_INLINE void point_store(uint4* p, const ge_cached& c) const {
     uint32_t w[40];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      w[i] = c.YpX.v[i]; w[10 + i] = c.YmX.v[i]; w[20 + i] = c.Z2.v[i]; w[30 + i] = c.T2d.v[i];
-    }
-#pragma unroll
-    for (int q = 0; q < 10; ++q) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+    words_of_cached(w, c);
+    st_quads<10>(p, w);
   }
   NT_D NT_INLINE void tab_store(uint32_t idx, uint32_t t, uint32_t j, const ge_cached& c) const {
     point_store(point(idx, t, j), c);
@@ -397,11 +315,7 @@ struct DevKTab {
   }
   NT_D NT_INLINE void point_load_signed(const uint4* p, uint32_t a, bool neg, ge_cached& c) const {
     uint32_t w[40];
-#pragma unroll
-    for (int q = 0; q < 10; ++q) {
-      const uint4 v = p[q];
-      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-    }
+    ld_quads<10>(w, p);
     ge_cached z;
     ge_cached_0(z);
 #pragma unroll
@@ -436,26 +350,17 @@ struct KsStash {
     uint32_t w[40];
 #pragma unroll
     for (int i = 0; i < 10; ++i) { w[i] = P.X.v[i]; w[10 + i] = P.Y.v[i]; w[20 + i] = P.Z.v[i]; w[30 + i] = a.v[i]; }
-#pragma unroll
-    for (int q = 0; q < kKsQuads; ++q) *at(j, q) = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+    st_quads_at<kKsQuads>([&](int q) { return at(j, q); }, w);
   }
   NT_D NT_INLINE void get_point(int j, ge_p2& P) const {
     uint32_t w[32];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const uint4 v = *at(j, q);
-      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-    }
+    ld_quads_at<8>(w, [&](int q) { return at(j, q); });
 #pragma unroll
     for (int i = 0; i < 10; ++i) { P.X.v[i] = w[i]; P.Y.v[i] = w[10 + i]; P.Z.v[i] = w[20 + i]; }
   }
   NT_D NT_INLINE void get_prefix(int j, fe& a) const {
     uint32_t w[12];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const uint4 v = *at(j, 7 + q);
-      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-    }
+    ld_quads_at<3>(w, [&](int q) { return at(j, 7 + q); });
 #pragma unroll
     for (int i = 0; i < 10; ++i) a.v[i] = w[2 + i];
   }

@@ -215,7 +215,7 @@ struct Device {
   uint64_t xtab_reserved = 0;   // (entry) its bytes in the budget
   bool xtab_tried = false;      // (entry) under tables_mu
   std::atomic<int> xtab_ready{0};  // this slot's d_xtab / xslots are set
-  // The key-table cache (ed25519_ops.hpp KTab): one per device entry, shared like the x cache;
+  // The key-table cache (ktab.hpp): one per device entry, shared like the x cache;
   // ktab_for() (context.cpp) allocates it with the first verify -- the control block and the
   // index zero-filled, the pool as hipMalloc leaves it (a pool line is read only after a slot
   // names its entry) -- and never rewrites or frees an entry before the context closes.

@@ -542,18 +542,10 @@ NT_HD NT_INLINE void sc_unbalanced_t(uint32_t u[8], uint32_t& uneg, uint32_t v[8
 }
 NT_HD NT_INLINE void sc_unbalanced(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8], int& ubits,
                                    int& vbits) {
-#ifdef NT_LAT_ONE_STEP  // A/B builds only
-  sc_unbalanced_t<false>(u, uneg, v, k, ubits, vbits);
-#else
   sc_unbalanced_t<true>(u, uneg, v, k, ubits, vbits);
-#endif
 }
 NT_HD NT_INLINE int sc_halfsize(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8]) {
-#ifdef NT_LAT_ONE_STEP  // A/B builds only
-  return sc_halfsize_t<false>(u, uneg, v, k);
-#else
   return sc_halfsize_t<true>(u, uneg, v, k);
-#endif
 }
 NT_HD NT_INLINE int sc_halfsize_euclid(uint32_t u[8], uint32_t& uneg, uint32_t v[8], const uint32_t k[8]) {
   return sc_halfsize_t<false>(u, uneg, v, k);

@@ -900,7 +900,7 @@ def unbalanced_model(k):
 
 
 def windows3(ubits, vbits):
-    """the window count of a lane of the three-table ladder (ed25519_ops.hpp ladder_uv3)"""
+    """the window count of a lane of the three-table ladder (ktab_tables.hpp ladder_uv3)"""
     return min(64, max(16, (vbits + 5) >> 2, ((ubits + 5) >> 2) - 32))
 
 
@@ -1531,7 +1531,7 @@ def check_wcomb_refusals(run):
 
 # --------------------------------------------------------------------------
 # the key-table cache's comb path: ktab_build_comb, kc_recode / kc_pick, ladder_kc, compare_one,
-# verify_kc (ed25519_ops.hpp), over the runner's comb table
+# verify_kc (ktab_comb.hpp; compare_one: ed25519_ops.hpp), over the runner's comb table
 # --------------------------------------------------------------------------
 KC_CAPACITY = 80
 KC_EDGES = (0, 1, 2, 3, L - 1, L - 2, 1 << 252, (1 << 253) - 1, (1 << 253) - 2)
@@ -1558,7 +1558,7 @@ class Mul:
 
 
 def entry_scalar(block, index):
-    """the integer multiple of A that comb line 8 block + index holds (ed25519_ops.hpp, "The comb")"""
+    """the integer multiple of A that comb line 8 block + index holds (ktab_comb.hpp, "The comb")"""
     r = [1 if index >> t & 1 else -1 for t in range(3)]
     return (1 << 16 * block) * ((1 << 192) + r[2] * (1 << 128) + r[1] * (1 << 64) + r[0])
 

@@ -1,5 +1,5 @@
 // kcomb_threads.cpp -- TEST INFRASTRUCTURE: the key-table cache's claim / build / publish /
-// probe code with a comb pool (ed25519_ops.hpp ktab_probe, ktab_sight, ktab_build -> ktab_build_comb)
+// probe code with a comb pool (ktab.hpp ktab_probe, ktab_sight; ktab_build -> ktab_comb.hpp ktab_build_comb)
 // and the cached check over it (verify_kc), run by several host threads at once over one index, one
 // pool and one comb pool, with host atomics (host_kcomb.hpp).  Every thread walks the same keys in
 // its own order; whenever a key's slot reads ready, the entry's tag and all 33 comb lines must be

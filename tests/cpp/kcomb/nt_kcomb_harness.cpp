@@ -1,6 +1,6 @@
 // nt_kcomb_harness.cpp -- TEST INFRASTRUCTURE: the comb path of the verify kernel's key-table
-// cache on the host (ed25519_ops.hpp ktab_build with a comb pool, kc_recode / kc_pick, ladder_kc,
-// verify_kc) over memory the test owns.  Never linked into libntcrypto.so.
+// cache on the host (ed25519_ops.hpp ktab_build with a comb pool; ktab_comb.hpp kc_recode / kc_pick,
+// ladder_kc, verify_kc) over memory the test owns.  Never linked into libntcrypto.so.
 #include "kc_common.hpp"
 
 namespace {

@@ -1,5 +1,5 @@
 // host_ktab.hpp -- TEST INFRASTRUCTURE: the key-table cache of the verify kernel
-// (ed25519_ops.hpp KTab) over plain host memory with host atomics, laid out like
+// (ktab.hpp) over plain host memory with host atomics, laid out like
 // the device's (kernels_common.hpp DevKTab): 8-byte index slots, pool entries of
 // kKtEntryBytes (128-B header: 8 tag words + flags; then 3 x 8 points of 40
 // words), a control block {bump counter, fast rows, builds, old-path rows}.

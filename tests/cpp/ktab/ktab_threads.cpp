@@ -1,5 +1,5 @@
 // ktab_threads.cpp -- TEST INFRASTRUCTURE: the key-table cache's claim / build /
-// publish / probe code (ed25519_ops.hpp ktab_probe, ktab_sight, ktab_build) run by
+// publish / probe code (ktab.hpp ktab_probe, ktab_sight; ktab_tables.hpp ktab_build) run by
 // several host threads at once over one index and one pool, with host atomics
 // (host_ktab.hpp).  Every thread walks the same keys in its own order; whenever a
 // key's slot reads ready, the entry's tag and all 24 table points must be the

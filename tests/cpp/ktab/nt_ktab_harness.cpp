@@ -1,5 +1,5 @@
 // nt_ktab_harness.cpp -- TEST INFRASTRUCTURE: the unbalanced lattice vector
-// (sc25519.hpp sc_unbalanced), the three-table ladder (ed25519_ops.hpp
+// (sc25519.hpp sc_unbalanced), the three-table ladder (ktab_tables.hpp
 // verify_uv3) and the key-table cache (KTab) on the host, over memory the test
 // owns and may fill with whatever it likes.  Built on the host harness
 // (../nt_host_harness.cpp: its HostATab and its comb of B), which is included as

@@ -1,6 +1,6 @@
 // nt_ktab4_harness.cpp -- TEST INFRASTRUCTURE: the four-table path of the verify kernel's
-// key-table cache on the host (ed25519_ops.hpp ktab_build with an extension, ladder_k4,
-// verify_k4, compare_one) over memory the test owns.  Never linked into libntcrypto.so.
+// key-table cache on the host (ktab_tables.hpp ktab_build with an extension, ladder_k4,
+// verify_k4; ed25519_ops.hpp compare_one) over memory the test owns.  Never linked into libntcrypto.so.
 #include "k4_common.hpp"
 
 namespace {

@@ -298,8 +298,8 @@ NT_HD NT_INLINE void item_ladder_uv3(size_t i, const uint32_t* kidx, const uint3
   if (write) st_w<8>(out8, i, o);
 }
 
-// ---- the key-table cache's comb path (ed25519_ops.hpp ktab_build_comb, kc_recode / kc_pick,
-// ladder_kc, compare_one, verify_kc).  These items run over a second layout: the blob above,
+// ---- the key-table cache's comb path (ktab_comb.hpp ktab_build_comb, kc_recode / kc_pick,
+// ladder_kc, verify_kc; ed25519_ops.hpp compare_one).  These items run over a second layout: the blob above,
 // words 8..9 of its control block carrying the comb pool's address, then `capacity` combs of
 // kKtCombBytes, then kKcProbeGuardBytes that nothing may write (the caller prefills pool, combs
 // and guard and reads them back).  The three-table items above keep their blob (words 8..9

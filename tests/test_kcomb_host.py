@@ -1,5 +1,5 @@
 """The key-table cache's comb path on the host (tests/cpp/kcomb/): the recoding of the full hash
-scalar into 64 signed lookups (ed25519_ops.hpp kc_recode / kc_pick), the 33 affine lines that
+scalar into 64 signed lookups (ktab_comb.hpp kc_recode / kc_pick), the 33 affine lines that
 ktab_build stores for a key, the 15-doubling ladder over them (ladder_kc), the verdicts of
 verify_kc and of the whole path (verify_n) with a cold cache, and the stand-alone programs under
 the sanitizers."""

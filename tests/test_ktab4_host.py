@@ -1,5 +1,5 @@
 """The key-table cache's four-table path on the host (tests/cpp/ktab4/): ktab_build with an
-extension pool, the 16-window ladder over the full hash scalar (ed25519_ops.hpp ladder_k4), the
+extension pool, the 16-window ladder over the full hash scalar (ktab_tables.hpp ladder_k4), the
 check that compares R' = [s]B - [k]A with R's bytes after one inversion (verify_k4,
 compare_one), and a policy without an extension, whose bytes and paths stay what they were."""
 import ctypes

@@ -1,5 +1,5 @@
 """The verify kernel's key-table cache on the host (tests/cpp/ktab/): the unbalanced
-lattice vector (sc25519.hpp sc_unbalanced), the three-table ladder (ed25519_ops.hpp
+lattice vector (sc25519.hpp sc_unbalanced), the three-table ladder (ktab_tables.hpp
 verify_uv3) for every kind of valid vector, and the cache's states -- first sighting
 marks, second builds, third hits -- over an index and a pool the test owns and may
 corrupt.  A verdict never depends on the cache; only the path does."""
