@@ -1,6 +1,6 @@
 """ctypes binding of tests/cpp/build/libntprobe.so -- the device functions of
-narwhal-tusk_amd/csrc/*.hpp behind one gfx950 kernel each (TEST INFRASTRUCTURE;
-see tests/cpp/nt_device_probe.hip).  build() compiles the library; a GPU test run
+narwhal-tusk_amd/csrc/*.hpp behind gfx950 kernels (TEST INFRASTRUCTURE; see
+tests/cpp/nt_device_probe.hip and the entry points of tests/cpp/nt_probe_entries.inc).  build() compiles the library; a GPU test run
 never does: a missing or stale library fails the test at once."""
 import ctypes
 import glob
@@ -18,7 +18,7 @@ _lib = None
 
 
 def sources():
-    return [os.path.join(CPP, "nt_device_probe.hip"), os.path.join(CPP, "nt_probe_items.hpp")] + \
+    return [os.path.join(CPP, f) for f in ("nt_device_probe.hip", "nt_probe_items.hpp", "nt_probe_entries.inc")] + \
         sorted(glob.glob(os.path.join(CSRC, "*.hpp")))
 
 

@@ -6,10 +6,13 @@
 // (c) check the wide-comb construction (wcomb_key_bases / wcomb_fill, driven through
 // wcomb_fill_target and wcomb_fill_launch of wcomb_build.hpp), digit schedule and sums
 // against an independent curve model, and (d) count field multiplies per operation
-// (profiles/opcount.json, the roofline numerator).
+// (profiles/opcount.json, the roofline numerator).  It is also the host runner of the
+// arithmetic probe: the nthb_* entry points at the end of the file are those of the device
+// probe (nt_probe_entries.inc, shared with nt_device_probe.hip) over a loop.
 // Never linked into libntcrypto.so.
 #define NT_OPCOUNT 1
 #include <cstring>
+#include <tuple>
 #include <unordered_map>
 
 #ifdef NT_LAT_RCP_MODEL
@@ -623,173 +626,7 @@ void nth_key_table_find(const uint8_t* keys, uint32_t nkeys, unsigned long long 
 }
 }
 
-// ---- host twins of the device probe (nt_device_probe.hip): the same item functions
-// (nt_probe_items.hpp) in a loop over n items, same argument lists as the ntp_* entry points
 extern "C" {
-int nthb_fe_mul(uint64_t n, const uint32_t* f, const uint32_t* g, uint32_t* out) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_mul(i, f, g, out);
-  return 0;
-}
-int nthb_fe_sq(uint64_t n, const uint32_t* f, uint32_t* out) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_sq(i, f, out);
-  return 0;
-}
-int nthb_fe_sq_wide(uint64_t n, const uint32_t* f, uint32_t* out) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_sq_wide(i, f, out);
-  return 0;
-}
-int nthb_fe_carry(uint64_t n, const uint32_t* f, uint32_t* out) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_carry(i, f, out);
-  return 0;
-}
-int nthb_fe_tobytes(uint64_t n, const uint32_t* f, uint32_t* out8) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_tobytes(i, f, out8);
-  return 0;
-}
-int nthb_fe_frombytes(uint64_t n, const uint32_t* in8, uint32_t* out) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_frombytes(i, in8, out);
-  return 0;
-}
-int nthb_fe_invert(uint64_t n, const uint32_t* f, uint32_t* out8, int vt) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_fe_invert(i, f, out8, vt);
-  return 0;
-}
-int nthb_sc_reduce512(uint64_t n, const uint32_t* in16, uint32_t* out8) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_reduce512(i, in16, out8);
-  return 0;
-}
-int nthb_sc_muladd(uint64_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out8) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_muladd(i, a, b, c, out8);
-  return 0;
-}
-int nthb_sc_mul(uint64_t n, const uint32_t* a, const uint32_t* b, uint32_t* out8) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_mul(i, a, b, out8);
-  return 0;
-}
-int nthb_sc_reduce_half(uint64_t n, const uint32_t* k8, uint32_t* out8, uint32_t* neg) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_reduce_half(i, k8, out8, neg);
-  return 0;
-}
-int nthb_sc_recode_w4(uint64_t n, const uint32_t* s8, uint32_t* out8) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_recode_w4(i, s8, out8);
-  return 0;
-}
-int nthb_sc_is_canonical(uint64_t n, const uint32_t* s8, uint32_t* out1) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_is_canonical(i, s8, out1);
-  return 0;
-}
-// lehmer 1: sc_halfsize_t<true> (the kernels'), 0: sc_halfsize_t<false> = sc_halfsize_euclid
-int nthb_sc_halfsize(uint64_t n, const uint32_t* k8, uint32_t* u8, uint32_t* uneg, uint32_t* v8, int32_t* bits,
-                     int lehmer) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_halfsize(i, k8, u8, uneg, v8, bits, lehmer);
-  return 0;
-}
-int nthb_hram(uint64_t n, const uint32_t* R8, const uint32_t* A8, const uint8_t* msg, uint64_t msg_bytes,
-              const uint64_t* off, const uint64_t* len, uint32_t* out8, int fast) {
-  for (uint64_t i = 0; i < n; ++i)
-    if (!msg_slice(off[i], len[i], msg_bytes).ok) return 1;
-  // load_words reads whole 4-byte granules: an aligned copy with room past the end
-  std::vector<uint32_t> buf(msg_bytes / 4 + 8, 0u);
-  if (msg_bytes) std::memcpy(buf.data(), msg, msg_bytes);
-  for (uint64_t i = 0; i < n; ++i) ntp::item_hram(i, R8, A8, (const uint8_t*)buf.data(), off, len, out8, fast);
-  return 0;
-}
-int nthb_point_checks(uint64_t n, const uint32_t* enc8, uint32_t* out4) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_point_checks(i, enc8, out4);
-  return 0;
-}
-// per item with the item's own window count (wave_max is the identity on the host)
-int nthb_ladder_uv(uint64_t n, const uint32_t* A8, const uint32_t* R8, const uint32_t* u8, const uint32_t* uneg,
-                   const uint32_t* v8, const int32_t* bits, uint32_t* out8) {
-  for (uint64_t i = 0; i < n; ++i) {
-    if (bits[i] < 0 || bits[i] > 253) return 1;
-    HostATab at;
-    ntp::item_ladder_uv(i, A8, R8, u8, uneg, v8, bits, at, out8, true);
-  }
-  return 0;
-}
-// lehmer 1: sc_unbalanced_t<true> (verify_one_kt's), 0: the one-step loop
-int nthb_sc_unbalanced(uint64_t n, const uint32_t* k8, uint32_t* u8, uint32_t* uneg, uint32_t* v8, int32_t* ubits,
-                       int32_t* vbits, int lehmer) {
-  for (uint64_t i = 0; i < n; ++i) ntp::item_sc_unbalanced(i, k8, u8, uneg, v8, ubits, vbits, lehmer);
-  return 0;
-}
-// The key-table items over HostKTab (ktab/host_ktab.hpp) on the caller's blob, which has the
-// device's layout: control block, ntp::kKtProbeSlots index slots, `capacity` pool entries.
-static HostKTab blob_ktab(uint8_t* blob, uint32_t capacity) {
-  return HostKTab{(uint64_t*)(blob + ntp::kKtProbeCtlBytes), ntp::kKtProbeSlots - 1u, blob + ntp::kKtProbePoolOff,
-                  capacity, (uint32_t*)blob};
-}
-int nthb_ktab_fill(uint64_t n, const uint32_t* A8, uint8_t* blob, uint32_t capacity, uint32_t* slot) {
-  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap) return 1;
-  const HostKTab kt = blob_ktab(blob, capacity);
-  for (uint64_t i = 0; i < n; ++i) ntp::item_ktab_fill(i, A8, kt, slot, true);
-  return 0;
-}
-int nthb_ktab_point(uint64_t n, const uint32_t* A8, const int32_t* td2, uint8_t* blob, uint32_t capacity,
-                    uint32_t* out3, uint32_t* enc8) {
-  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap || !ntp::ktab_point_args_ok(n, td2)) return 1;
-  const HostKTab kt = blob_ktab(blob, capacity);
-  for (uint64_t i = 0; i < n; ++i) ntp::item_ktab_point(i, A8, td2, kt, out3, enc8);
-  return 0;
-}
-// per item with the item's own window count (wave_max is the identity on the host)
-int nthb_ladder_uv3(uint64_t n, const uint32_t* kidx, const uint32_t* R8, const uint32_t* u8, const uint32_t* v8,
-                    const uint32_t* sc4, uint8_t* blob, uint32_t capacity, uint32_t* out8) {
-  if (capacity < 1 || capacity > ntp::kKtProbeMaxCap || !ntp::ladder_uv3_args_ok(n, kidx, sc4, capacity)) return 1;
-  const HostKTab kt = blob_ktab(blob, capacity);
-  for (uint64_t i = 0; i < n; ++i) {
-    HostATab at;
-    ntp::item_ladder_uv3(i, kidx, R8, u8, v8, sc4, at, kt, out8, true);
-  }
-  return 0;
-}
-
-// The comb items over HostKComb (kcomb/host_kcomb.hpp) on the caller's comb blob: the layout
-// above, then `capacity` combs and the guard (ntp::kcomb_probe_bytes); same argument lists and
-// the same argument checks as the probe's entry points (1 where the probe returns an error).
-static HostKComb blob_kcomb(uint8_t* blob, uint32_t capacity) {
-  return HostKComb((uint64_t*)(blob + ntp::kKtProbeCtlBytes), ntp::kKtProbeSlots - 1u, blob + ntp::kKtProbePoolOff, capacity,
-                   (uint32_t*)blob, blob + ntp::kcomb_probe_comb_off(capacity));
-}
-int nthb_kcomb_fill(uint64_t n, const uint32_t* A8, uint8_t* blob, uint32_t capacity, uint32_t* slot) {
-  if (!ntp::kcomb_cap_ok(capacity)) return 1;
-  const HostKComb kt = blob_kcomb(blob, capacity);
-  for (uint64_t i = 0; i < n; ++i) {
-    HostATab at;
-    ntp::item_kcomb_fill(i, A8, kt, at, slot, true);
-  }
-  return 0;
-}
-int nthb_kcomb_line(uint64_t n, const uint32_t* A8, const uint32_t* line, uint8_t* blob, uint32_t capacity, uint32_t* out3,
-                    uint32_t* limbs30) {
-  if (!ntp::kcomb_cap_ok(capacity)) return 1;
-  const HostKComb kt = blob_kcomb(blob, capacity);
-  for (uint64_t i = 0; i < n; ++i) ntp::item_kcomb_line(i, A8, line, kt, out3, limbs30);
-  return 0;
-}
-int nthb_kc_picks(uint64_t n, const uint32_t* k8, uint32_t* out65) {
-  if (!ntp::kc_scalars_ok(n, k8)) return 1;
-  uint64_t slots[kKtBucket] = {};
-  uint32_t ctl[4] = {};
-  const HostKComb kt(slots, kKtBucket - 1, nullptr, 0, ctl, nullptr);
-  for (uint64_t i = 0; i < n; ++i) ntp::item_kc_picks(i, k8, kt, out65);
-  return 0;
-}
-int nthb_ladder_kc(uint64_t n, const uint32_t* kidx, const uint32_t* k8, const uint32_t* dead, uint8_t* blob,
-                   uint32_t capacity, uint32_t* out8) {
-  if (!ntp::kcomb_cap_ok(capacity) || !ntp::ladder_kc_args_ok(n, kidx, k8, dead, capacity)) return 1;
-  const HostKComb kt = blob_kcomb(blob, capacity);
-  for (uint64_t i = 0; i < n; ++i) ntp::item_ladder_kc(i, kidx, k8, dead, kt, out8, true);
-  return 0;
-}
-int nthb_compare_one(uint64_t n, const uint32_t* x8, const uint32_t* y8, const uint32_t* z8, const uint32_t* R8,
-                     const uint32_t* mode, uint32_t* out1) {
-  if (!ntp::modes_ok(n, mode)) return 1;
-  for (uint64_t i = 0; i < n; ++i) ntp::item_compare_one(i, x8, y8, z8, R8, mode, out1);
-  return 0;
-}
-
 // How often fe_invert_vt's matrix application comes out negative for the value z (10 limbs),
 // i.e. how often gcd_lincomb_shift takes its negation branch (fe_inv_vt.hpp: about once in
 // 3,000 inversions).  The outer loop of fe_invert_vt is restated here around the header's own
@@ -851,11 +688,11 @@ int nth_gcd_neg_count(const uint32_t* f) {
 }
 }
 
-// ---- host twins of the probe's wide-comb entry points (nt_device_probe.hip), same argument
-// lists and the same argument checks (ntp::*_args_ok; 1 where the probe returns an error).
-// Digits, sums and key sums run over HostWComb (entries by double-and-add) at all five
-// widths.  Table entries come from the product's construction: at 16 bits from whole combs
-// (67 MB per key) built as wcomb_build<W> builds them -- wcomb_key_bases per key, then per
+// ---- host twins of the probe's hand-written wide-comb entry points (nt_device_probe.hip), same
+// argument lists and the same argument checks (ntp::*_args_ok; 1 where the probe returns an
+// error); the two sides differ by more than their runner, so they are not in nt_probe_entries.inc.
+// Sums and key sums run over HostWComb (entries by double-and-add) at all five widths.  Table
+// entries come from the product's construction: at 16 bits from whole combs (67 MB per key) built as wcomb_build<W> builds them -- wcomb_key_bases per key, then per
 // batch (wcomb_fill_launch) every thread of the launch's grid through wcomb_fill_target and
 // wcomb_fill, into an allocation pre-filled with 0xA5 with a guard behind it -- over which the
 // sums run a second time (2: the two disagree); at the other widths from single chunks,
@@ -994,12 +831,6 @@ int nthb_wcomb_guard(uint32_t* out1) {
   *out1 = g_hwc.table.empty() || words_intact(g_hwc.table.data() + g_hwc.table.size() - kGuardWords, kGuardWords);
   return 0;
 }
-int nthb_wcomb_digits(int bits, uint64_t n, const uint32_t* x8, uint32_t* out) {
-  const bool ok = ntp::wcomb_width(bits, [&](auto w) {
-    for (uint64_t i = 0; i < n; ++i) ntp::item_wcomb_digits<decltype(w)::value>(i, x8, out);
-  });
-  return ok ? 0 : 1;
-}
 int nthb_wcomb_entries(uint64_t n, const uint32_t* key, const uint32_t* pos, const uint32_t* idx, uint32_t* out32) {
   int rc = 1;
   ntp::wcomb_width(g_hwc.bits, [&](auto w) {
@@ -1056,21 +887,6 @@ int nthb_key_comb_sum(uint64_t n, const uint32_t* key, const uint32_t* meta, con
   });
   return rc;
 }
-// verify_kc over the comb blob with the live comb set's key 0 as the comb of B: the narrowest
-// width, built of B alone (nthb_wcomb_build), as the probe's entry point asks for it
-int nthb_verify_kc(uint64_t n, const uint32_t* kidx, const uint32_t* kflags, const uint32_t* R8, const uint32_t* S8,
-                   const uint32_t* k8, const uint32_t* mode, uint8_t* blob, uint32_t capacity, uint32_t* out1) {
-  constexpr int W = kKeyCombNarrow;
-  if (g_hwc.bits != W || host_combs<W>().empty() || !ntp::kcomb_cap_ok(capacity) ||
-      !ntp::verify_kc_args_ok(n, kidx, kflags, k8, mode, capacity))
-    return 1;
-  for (uint64_t i = 0; i < n; ++i)
-    if (!ntp::wcomb_scalar_ok<W>(S8 + 8 * i)) return 1;
-  const HostKComb kt(blob_kcomb(blob, capacity));
-  const HostCombRef<HostWComb<W>> wb{&host_combs<W>()[0]};
-  for (uint64_t i = 0; i < n; ++i) ntp::item_verify_kc(i, kidx, kflags, R8, S8, k8, mode, wb, kt, out1, true);
-  return 0;
-}
 // wcomb_fill_target of n threads t of a fill launch over nkeys keys: out = live, key, pos,
 // chunk, dst, tmp (6 words per thread); geom = kPos, kChunks, kEntries, kWordsPerPoint,
 // kCorrWord, then comb_size(bits, 0 .. 3)
@@ -1100,3 +916,58 @@ int nth_wcomb_fill_launch(int bits, uint32_t k0, uint32_t total, uint32_t batch,
   return ok ? 0 : 1;
 }
 }
+
+// ---- the host runner of the probe's per-item entry points (nt_probe_entries.inc, shared with
+// nt_device_probe.hip: here they are nthb_*): the same item functions (nt_probe_items.hpp) in a
+// loop over n items.  form() is what a described argument is for the whole call, each() what
+// item i gets of it.
+namespace {
+using namespace ntp;
+template <class T>
+const T* form(In<T> a) { return a.p; }
+template <class T>
+T* form(Out<T> a) { return a.p; }
+// HostKTab (ktab/host_ktab.hpp) and HostKComb (kcomb/host_kcomb.hpp) on the caller's blob, which
+// has the device's layout: control block, kKtProbeSlots index slots, `cap` pool entries, and for
+// the comb items `cap` combs and the guard (kcomb_probe_bytes)
+HostKTab form(Blob<false> b) {
+  return HostKTab{(uint64_t*)(b.p + kKtProbeCtlBytes), kKtProbeSlots - 1u, b.p + kKtProbePoolOff, b.cap, (uint32_t*)b.p};
+}
+HostKComb form(Blob<true> b) {
+  return HostKComb((uint64_t*)(b.p + kKtProbeCtlBytes), kKtProbeSlots - 1u, b.p + kKtProbePoolOff, b.cap, (uint32_t*)b.p,
+                   b.p + kcomb_probe_comb_off(b.cap));
+}
+HostKComb form(NoTable) { return HostKComb(nullptr, 0, nullptr, 0, nullptr, nullptr); }  // its dig[] alone
+// load_words reads whole 4-byte granules: an aligned copy with room past the end
+std::vector<uint32_t> form(Msg m) {
+  std::vector<uint32_t> buf(m.bytes / 4 + 8, 0u);
+  if (m.bytes) std::memcpy(buf.data(), m.p, m.bytes);
+  return buf;
+}
+template <class V>
+V form(V v) { return v; }  // Ws, a Const, the comb of B: as it is
+
+template <class F>
+F& each(F& f) { return f; }
+HostATab each(Ws&) { return HostATab{}; }  // a fresh table workspace per item
+const uint8_t* each(std::vector<uint32_t>& buf) { return (const uint8_t*)buf.data(); }
+
+// every item is live: a Repeat entry's items get true for their trailing bool
+template <class Tail, class Item, class... A>
+int run(uint64_t n, Item item, A... a) {
+  std::tuple<decltype(form(a))...> f{form(a)...};
+  for (uint64_t i = 0; i < n; ++i)
+    std::apply([&](auto&... x) {
+      if constexpr (std::is_same<Tail, Repeat>::value) item(i, each(x)..., true);
+      else item(i, each(x)...);
+    }, f);
+  return 0;
+}
+
+// key 0 of the live comb set as verify_kc's comb of B: the narrowest width, built of B alone
+bool live_bcomb_ok() { return g_hwc.bits == kKeyCombNarrow && !host_combs<kKeyCombNarrow>().empty(); }
+HostCombRef<HostWComb<kKeyCombNarrow>> live_bcomb() { return {&host_combs<kKeyCombNarrow>()[0]}; }
+}  // namespace
+
+#define NTP_NAME(name) nthb_##name
+#include "nt_probe_entries.inc"

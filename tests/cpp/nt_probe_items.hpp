@@ -3,7 +3,9 @@
 // (the gfx950 build of narwhal-tusk_amd/csrc/*.hpp) and in a loop by
 // nt_host_harness.cpp (the same headers compiled by g++).  Each function is a
 // thin wrapper: it moves item i's words in and out of flat arrays and calls the
-// header function under test; no arithmetic lives here.
+// header function under test; no arithmetic lives here.  The entry points around
+// the items are written once too (nt_probe_entries.inc); how they describe an item's
+// arguments to the two runners is at the end of this file.
 // Field elements are 10 limbs, encodings and scalars 8 little-endian words.
 #pragma once
 #include <type_traits>
@@ -610,6 +612,48 @@ inline bool wcomb_build_args_ok(int bits, uint32_t nkeys, int negate, uint32_t b
   if (!wcomb_width(bits, [](auto) {})) return false;
   if (nkeys < 1 || nkeys > kWcMaxKeys || batch < 1) return false;
   return bits != kBCombBits || (nkeys == 1 && !negate);
+}
+
+// ---- how an entry point (nt_probe_entries.inc) describes item i's arguments to its runner's
+// run<Tail>(n, item, args...): the arguments stand in the item's own order, and each runner
+// (nt_device_probe.hip, nt_host_harness.cpp) turns a description into what its items take.
+// Anything that is none of the descriptions below goes to the item as it is.
+struct Leave {};   // lanes past n leave at once
+struct Repeat {};  // lanes past n run item n - 1 with false for the item's trailing bool: they write nothing
+template <class T>
+struct In {  // the caller's input, `bytes` per item
+  const T* p;
+  size_t bytes;
+};
+template <class T>
+struct Out {  // the caller's output, `bytes` per item
+  T* p;
+  size_t bytes;
+};
+template <class T>
+inline In<T> in(const T* p, size_t bytes) { return {p, bytes}; }
+template <class T>
+inline Out<T> out_(T* p, size_t bytes) { return {p, bytes}; }
+struct Ws {};  // the lane's [k]A table workspace
+template <bool COMB>
+struct Blob {  // the caller's key table of `cap` entries, read and written; COMB: with the comb pool and guard
+  uint8_t* p;
+  uint32_t cap;
+  size_t bytes() const { return COMB ? kcomb_probe_bytes(cap) : ktab_probe_bytes(cap); }
+};
+struct NoTable {};  // the key-table policy with no table behind it: its digit cells alone
+struct Msg {        // hram's message buffer: the items get a zero-padded, aligned copy
+  const uint8_t* p;
+  uint64_t bytes;
+};
+// a run-time switch as a compile-time constant: the items' int arguments fold, a width selects the template
+template <int V>
+using Const = std::integral_constant<int, V>;
+template <class F>
+inline int flag(int v, F&& f) { return v ? f(Const<1>{}) : f(Const<0>{}); }
+template <int W>
+NT_HD NT_INLINE void item_wcomb_digits(size_t i, const uint32_t* x8, uint32_t* out, Const<W>) {
+  item_wcomb_digits<W>(i, x8, out);
 }
 
 }  // namespace ntp

@@ -171,6 +171,18 @@ def test_comb_items_under_the_sanitizers():
     assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
 
 
+def test_shared_entry_points_under_the_sanitizers():
+    """The stand-alone program (its own main, -fsanitize=address,undefined, run directly): every
+    entry of nt_probe_entries.inc on the host runner at n = 0, 1 and 65, on heap buffers of exactly
+    the described sizes, byte for byte against a direct loop over the same items; every refusal of
+    the argument checks returns non-zero and leaves outputs and blob untouched."""
+    import subprocess
+    subprocess.run(["make", "-s", "-C", H.CPP, "build/probe_entries_check"], check=True)
+    r = subprocess.run([os.path.join(H.CPP, "build", "probe_entries_check")], capture_output=True, text=True)
+    print(r.stdout.strip())
+    assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
+
+
 def _fill_targets(bits, nkeys, t):
     """wcomb_fill_target of the threads t: (live, key, pos, chunk, dst, tmp) columns and the width's
     geometry (kPos, kChunks, kEntries, kWordsPerPoint, kCorrWord, comb / bases / tmp bytes per key, batch)"""
